@@ -30,6 +30,9 @@ Extra objects on that line:
                 else the plain-C oracle ("port").  `value` is ONE core (the reference is single-threaded);
                 `all_cores` runs one process per host core on disjoint slices (process sharding).  Rank 0, N = 1 only.
   cli_end_to_end  FASTA file -> .predict, the reference CLI against integration/glimmer-mg_gpu (N = 1, when both are built).
+  --dump-outputs DIR  (rank 0, after the timed region) what the last timed step left in the table: frame_scores.npy, float64
+                [k, 6, L] = the six frame rows of k reads of the last batch (all of them when the table fits 64 MB, else a fixed
+                seeded sample of DUMP_READS reads), and frame_scores_reads.npy, float64 [k] = those reads' indices in the batch.
   extras        (N = 1, after the timed region, in a process of its own: tests/bench/bench_extras.py) the other device paths of
                 SURVEY section 8(f) on 1M reads, 3 warm-ups + 10 calls each, every leg with its own `roofline` object and a sampled
                 check against the oracle: gmg_mg_score_reads (500 bp, ragged, -i, -s), gmg_mg_score_groups (64 ICMs x 100 null
@@ -51,6 +54,8 @@ SEED = 20260101
 MODEL = os.path.join(ROOT, "tests", "golden", "data", "NC_000915.icm")
 REF_BENCH = os.path.join(ROOT, "oracle", "_ref", "ref_bench")
 GENOME = os.path.join(ROOT, "tests", "golden", "data", "NC_000915.fna")
+DUMP_BYTES = 64 << 20                     # --dump-outputs: at most this much in all
+DUMP_READS = 2048                         # ... and this many sampled reads when the whole table is larger
 
 
 # ----------------------------------------------------------------------------------------------
@@ -212,6 +217,22 @@ def device_digest(out, total, first_read, n_reads, L):
     return "%016x" % int(np.bitwise_xor.reduce(x)), "%016x" % mix
 
 
+def dump_outputs(path, out, n, L):
+    """the six-frame table of the last call (reads [0, n) of the last batch, 6 rows of n * L doubles at the buffer's start) as
+    DIR/frame_scores.npy [k, 6, L]: every read when that fits DUMP_BYTES, else DUMP_READS reads drawn with a fixed seed"""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    if n * 6 * L * 8 + n * 8 <= DUMP_BYTES:
+        rows = np.arange(n, dtype=np.int64)
+    else:
+        rows = np.sort(np.random.default_rng(SEED).choice(n, size=min(DUMP_READS, n), replace=False)).astype(np.int64)
+    cols = (torch.from_numpy(rows)[:, None] * L + torch.arange(L)[None, :]).ravel().to(out.device)
+    table = out[:6 * n * L].view(6, n * L).index_select(1, cols).view(6, rows.size, L).permute(1, 0, 2)
+    np.save(os.path.join(path, "frame_scores.npy"), np.ascontiguousarray(table.cpu().numpy()))
+    np.save(os.path.join(path, "frame_scores_reads.npy"), rows.astype(np.float64))
+
+
 def extras(n_reads=1_000_000, reps=10):
     try:
         res = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench", "bench_extras.py"), str(n_reads), str(reps)],
@@ -255,7 +276,11 @@ def main():
                          "BASELINE configs[2]'s 12.5M reads per GPU = --reads 12500000 --batches 13; a step = all batches")
     ap.add_argument("--data", choices=("synthetic", "genome"), default="synthetic",
                     help="genome: reads cut uniformly from tests/golden/data/NC_000915.fna, both strands (weak scaling only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (rank 0; a seeded sample of at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
 
     # stdout carries ONE line, the JSON: whatever libraries write to file descriptor 1 on the way (RCCL prints a version banner
     # there when a process group is made) goes to stderr instead
@@ -355,6 +380,8 @@ def main():
                 ev.append((a, b))
 
     seconds, _ = timed_region(step, args.steps, args.warmup, torch.cuda.synchronize, dist)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, n, L)          # (n: the reads of the last batch, the table the last call wrote)
     per_call = sorted(a.elapsed_time(b) for a, b in ev[args.warmup:])
     kern_ms = per_call[len(per_call) // 2] if per_call else 0.0               # MEDIAN of the timed calls
     kern_min, kern_max = (per_call[0], per_call[-1]) if per_call else (0.0, 0.0)

@@ -7,8 +7,9 @@ Training sets copied as DATA fixtures (the reference's own sample-run files):
   tests/golden/data/seqs.cluster-{3,4}.run1.filt.gene.fasta   (sample-run/glimmer-mg/results/)
 For every case of CASES: the .icm the reference's build-icm writes -- whole when small, else its sha256 -- in
   tests/golden/train/<name>.icm | <name>.sha256 ; the cases themselves in tests/golden/train/cases.json.
-The big case (sample-run/glimmer3/results/NC_000915.train, 1.3 MB) is checked here against the oracle and recorded
-by sha256 only when the file is present; it does not travel.
+The big case (sample-run/glimmer3/results/NC_000915.train, 1.3 MB) is recorded by sha256 only; the file does not travel.
+The tests rebuild it from NC_000915.fna and the long-ORF list it was extracted from (sample-run/glimmer3/results/NC_000915.longorfs),
+kept as tests/golden/data/NC_000915.longorfs.npz: int32 start, stop, strand (+1 / -1).
 """
 import hashlib
 import json
@@ -88,13 +89,18 @@ def main():
         print(name, len(data), sha[:16])
     big = os.path.join(REF, "sample-run", "glimmer3", "results", "NC_000915.train")
     if os.path.exists(big):
+        import numpy as np
+        rows = [line.split()[1:4] for line in open(big[:-len("train")] + "longorfs")]
+        np.savez_compressed(os.path.join(DATA, "NC_000915.longorfs.npz"), start=np.array([int(r[0]) for r in rows], np.int32),
+                            stop=np.array([int(r[1]) for r in rows], np.int32),
+                            strand=np.array([1 if r[2][0] == "+" else -1 for r in rows], np.int32))
         with open(big, "rb") as fp:
             subprocess.run([BUILD_ICM, "-r", "/tmp/gmg_nc_train.icm"], stdin=fp, check=True)
         data = open("/tmp/gmg_nc_train.icm", "rb").read()
         cases.append({"name": "nc_r", "train": None, "opts": ["-r"], "model_len": 12, "model_depth": 7,
                       "periodicity": 3, "reversed": True, "whole": False, "text": False, "bytes": len(data),
                       "sha256": hashlib.sha256(data).hexdigest(),
-                      "note": "sample-run/glimmer3/results/NC_000915.train; checked where /root/reference exists"})
+                      "note": "sample-run/glimmer3/results/NC_000915.train, rebuilt by the tests from tests/golden/data/NC_000915.longorfs"})
     with open(os.path.join(OUT, "cases.json"), "w") as fp:
         json.dump(cases, fp, indent=1)
 

@@ -12,13 +12,33 @@ from conftest import DATA, GOLD
 
 TRAIN = os.path.join(GOLD, "train")
 CASES = json.load(open(os.path.join(TRAIN, "cases.json")))
-REF_BIG = "/root/reference/sample-run/glimmer3/results/NC_000915.train"
+LONG_ORFS = os.path.join(DATA, "NC_000915.longorfs.npz")    # long-orfs' list of the reference's sample run (glimmer3 on NC_000915)
+COMPLEMENT = str.maketrans("acgtrykmbvdhACGTRYKMBVDH", "tgcayrmkvbhdTGCAYRMKVBHD")
+
+
+def long_orf_training_set():
+    """the sample run's NC_000915.train: `extract -t` of every long ORF in NC_000915.fna -- from the first base of the start
+    codon up to the stop codon, stop codon left out, reverse complement for minus-strand frames (the genome is circular)"""
+    genome = "".join(line.strip() for line in open(os.path.join(DATA, "NC_000915.fna")) if not line.startswith(">"))
+    n_genome, twice = len(genome), genome + genome
+    orfs, seqs = np.load(LONG_ORFS), []
+    for start, stop, strand in zip(orfs["start"].tolist(), orfs["stop"].tolist(), orfs["strand"].tolist()):
+        if strand > 0:
+            n = (stop - start) % n_genome + 1 - 3
+            seqs.append(twice[start - 1:start - 1 + n])
+        else:
+            n = (start - stop) % n_genome + 1 - 3
+            lo = (start - n) % n_genome
+            seqs.append(twice[lo:lo + n].translate(COMPLEMENT)[::-1])
+    return seqs
 
 
 def training_strings(case, gmg):
     """build-icm's Read_Training_Data (src/ICM/build-icm.cc:320-340): lower case, then -r reverses every string"""
-    path = os.path.join(DATA, case["train"]) if case["train"] else REF_BIG
-    _, seqs = gmg.read_fasta(path)
+    if case["train"]:
+        _, seqs = gmg.read_fasta(os.path.join(DATA, case["train"]))
+    else:
+        seqs = long_orf_training_set()
     seqs = [s.lower().encode() for s in seqs]
     if "-F" in case["opts"]:         # Skip_In_Frame_Stop_Strings (build-icm.cc:80-109): default stop codons, before -r
         seqs = [s for s in seqs if not any(s[j:j + 3] in (b"taa", b"tag", b"tga") for j in range(0, len(s) - 2, 3))]
@@ -26,7 +46,7 @@ def training_strings(case, gmg):
 
 
 def binary_cases():
-    return [c for c in CASES if not c["text"] and (c["train"] or os.path.exists(REF_BIG))]
+    return [c for c in CASES if not c["text"]]
 
 
 @pytest.mark.parametrize("case", binary_cases(), ids=lambda c: c["name"])
