@@ -656,3 +656,120 @@ def window_distrib(model, windows, frames):
     for b in (dw, df, dd, dp):
         b.free()
     return dist, prob
+
+
+class FixedIcm:
+    """Fixed_Length_ICM_t (src/ICM/icm.hh:216-255) behind gmg_fixed_icm: a model read from a .fix file, or trained here as
+    build-fixed trains it (Fixed_Length_ICM_Training_t, the counting on the device)."""
+
+    def __init__(self, handle):
+        self.h = handle
+
+    @classmethod
+    def open(cls, path):
+        h = C.c_void_p()
+        _ck(capi.lib().gmg_fixed_icm_read(str(path).encode(), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def train(cls, strings, max_depth=7, special=-1, perm=None):
+        """build-fixed: strings of one length L (str / bytes, as read: case and ambiguity codes are Subscript's business),
+        depth max_depth, special position, permutation (None: none).  The caller's strings are not permuted."""
+        raw = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in strings]
+        arr = (C.c_char_p * max(len(raw), 1))(*raw)
+        p = None if perm is None else (C.c_int * len(perm))(*[int(x) for x in perm])
+        h = C.c_void_p()
+        _ck(capi.lib().gmg_fixed_icm_train(arr, len(raw), int(max_depth), int(special), p, C.byref(h)))
+        return cls(h)
+
+    def write(self, path, binary=True):
+        """Fixed_Length_ICM_Training_t::Output (binary, or the -t text); only for a model trained here"""
+        _ck(capi.lib().gmg_fixed_icm_write(self.h, str(path).encode(), 1 if binary else 0))
+
+    @property
+    def params(self):
+        """(length, max_depth, special_position, model_type, permutation list)"""
+        L, d, s, t = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        perm = (C.c_int * 32)()
+        _ck(capi.lib().gmg_fixed_icm_params(self.h, C.byref(L), C.byref(d), C.byref(s), C.byref(t), perm))
+        return L.value, d.value, s.value, t.value, list(perm[:L.value])
+
+    def score(self, strings, lo=0, hi=None):
+        """Fixed_Length_ICM_t::Score_Windows: subrange_score (s, lo, hi) of every string, ONE device call -> float64[n]"""
+        if hi is None:
+            hi = self.params[0]
+        raw = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in strings]
+        arr = (C.c_char_p * max(len(raw), 1))(*raw)
+        out = np.empty(len(raw), np.float64)
+        _ck(capi.lib().gmg_fixed_icm_score(self.h, arr, len(raw), int(lo), int(hi), _ptr(out)))
+        return out
+
+    def device(self):
+        """gmg_fixed_model handle (uploaded once, owned by this FixedIcm)"""
+        out = C.c_void_p()
+        _ck(capi.lib().gmg_fixed_icm_device_model(self.h, C.byref(out)))
+        return out
+
+    def close(self):
+        if self.h:
+            capi.lib().gmg_fixed_icm_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FixedModel:
+    """A gmg_fixed_model uploaded from tables: perm[L], and per sub-model i (mip int16 [N_i], prob float32 [N_i, 4], depth)."""
+
+    def __init__(self, perm, subs):
+        L = len(perm)
+        self._keep = [(np.ascontiguousarray(m, np.int16), np.ascontiguousarray(p, np.float32)) for m, p, _ in subs]
+        perm_a = np.ascontiguousarray(perm, np.int32)
+        mips = (C.c_void_p * max(L, 1))(*[m.ctypes.data for m, _ in self._keep])
+        probs = (C.c_void_p * max(L, 1))(*[p.ctypes.data for _, p in self._keep])
+        depth = np.array([d for _, _, d in subs], np.int32)
+        nodes = np.array([len(m) for m, _ in self._keep], np.int32)
+        self.h = C.c_void_p()
+        _ck(capi.lib().gmg_fixed_model_upload(L, _ptr(perm_a), mips, probs, _ptr(depth), _ptr(nodes), C.byref(self.h)))
+
+    def info(self):
+        L, d, b = C.c_int(), C.c_int(), C.c_uint64()
+        _ck(capi.lib().gmg_fixed_model_info(self.h, C.byref(L), C.byref(d), C.byref(b)))
+        return L.value, d.value, b.value
+
+    def device(self):
+        return self.h
+
+    def close(self):
+        if self.h:
+            capi.lib().gmg_fixed_model_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def fixed_score(model, reads, segs, lo=0, hi=None, d_out=None, stream=None):
+    """gmg_fixed_score: subrange_score (lo, hi) of the window at the start of every segment's buffer -> float64[n].
+    model: a FixedIcm or FixedModel.  With d_out (device pointer of n doubles) the call is asynchronous and returns None."""
+    h = model.device()
+    if hi is None:
+        L = C.c_int()
+        _ck(capi.lib().gmg_fixed_model_info(h, C.byref(L), None, None))
+        hi = L.value
+    if d_out is not None:
+        _ck(capi.lib().gmg_fixed_score(h, reads.h, segs.h, int(lo), int(hi), C.c_void_p(d_out), stream))
+        return None
+    buf = _DeviceBuffer(max(segs.n, 1) * 8)
+    _ck(capi.lib().gmg_fixed_score(h, reads.h, segs.h, int(lo), int(hi), buf.ptr, None))
+    _ck(capi.lib().gmg_synchronize(None))
+    out = buf.to_host(np.float64, segs.n)
+    buf.free()
+    return out

@@ -119,6 +119,10 @@ PROTOTYPES = {
     "gmg_trainer_create": (i32, [vp, i32, i32, i32, C.POINTER(vp)]),
     "gmg_trainer_level_counts": (i32, [vp, i32, vp, vp]),
     "gmg_trainer_free": (i32, [vp]),
+    "gmg_fixed_model_upload": (i32, [i32, vp, vp, vp, vp, vp, C.POINTER(vp)]),
+    "gmg_fixed_model_free": (i32, [vp]),
+    "gmg_fixed_model_info": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(u64)]),
+    "gmg_fixed_score": (i32, [vp, vp, vp, i32, i32, vp, vp]),
     "gmg_device_malloc": (i32, [C.POINTER(vp), C.c_size_t]),
     "gmg_device_free": (i32, [vp]),
     "gmg_memcpy_h2d": (i32, [vp, vp, C.c_size_t, vp]),
@@ -133,6 +137,13 @@ PROTOTYPES = {
     "gmg_icm_params": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     "gmg_icm_tables": (i32, [vp, vp, vp]),
     "gmg_icm_device_model": (i32, [vp, C.POINTER(vp)]),
+    "gmg_fixed_icm_read": (i32, [C.c_char_p, C.POINTER(vp)]),
+    "gmg_fixed_icm_train": (i32, [C.POINTER(C.c_char_p), i32, i32, i32, vp, C.POINTER(vp)]),
+    "gmg_fixed_icm_write": (i32, [vp, C.c_char_p, i32]),
+    "gmg_fixed_icm_params": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp]),
+    "gmg_fixed_icm_score": (i32, [vp, C.POINTER(C.c_char_p), i32, i32, i32, vp]),
+    "gmg_fixed_icm_device_model": (i32, [vp, C.POINTER(vp)]),
+    "gmg_fixed_icm_free": (i32, [vp]),
 }
 
 

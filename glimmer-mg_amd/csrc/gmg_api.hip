@@ -880,6 +880,7 @@ extern "C" int gmg_single_stage(gmg_single *st, const char *ascii, uint64_t n, i
     g.d_out_off = (uint64_t *)(d_tail + 16 + sizeof sg);
     g.n = 1;
     g.total_len = n;
+    g.min_len = n;
     st->in_flight = true;
     *reads = &r;
     *segs = &g;
@@ -943,6 +944,7 @@ extern "C" int gmg_segments_upload(const gmg_reads *reads, const gmg_segment *se
     GMG_HIP(hipMemcpy(off.data(), reads->d_off, off.size() * 8, hipMemcpyDeviceToHost));
     std::vector<uint64_t> pre(n + 1);
     pre[0] = 0;
+    uint64_t min_len = n ? UINT64_MAX : 0;
     for (uint64_t i = 0; i < n; i++) {
         const gmg_segment &s = segs[i];
         if (s.read >= reads->n_reads || s.orient > GMG_REVCOMP)
@@ -953,12 +955,14 @@ extern "C" int gmg_segments_upload(const gmg_reads *reads, const gmg_segment *se
             return gmg_set_error(GMG_ERANGE, "gmg_segments_upload: segment %llu [%u,+%u) leaves read %u of length %llu",
                                  (unsigned long long)i, s.lo, s.len, s.read, (unsigned long long)L);
         pre[i + 1] = pre[i] + s.len;
+        if (s.len < min_len) min_len = s.len;
     }
     gmg_segments *g = new (std::nothrow) gmg_segments();
     if (!g) return gmg_set_error(GMG_ENOMEM, "gmg_segments_upload: out of host memory");
     memset(g, 0, sizeof *g);
     g->n = n;
     g->total_len = pre[n];
+    g->min_len = min_len;
     hipError_t e = hipMalloc((void **)&g->d_segs, (n ? n : 1) * sizeof(gmg_segment));
     if (e == hipSuccess) e = hipMalloc((void **)&g->d_out_off, (n + 1) * 8);
     if (e == hipSuccess && n) e = hipMemcpy(g->d_segs, segs, n * sizeof(gmg_segment), hipMemcpyHostToDevice);

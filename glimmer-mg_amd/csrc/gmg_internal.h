@@ -77,6 +77,7 @@ struct gmg_segments {
     uint64_t *d_out_off;         // n + 1, exclusive prefix of len
     uint64_t n;
     uint64_t total_len;
+    uint64_t min_len;            // shortest segment (gmg_fixed_score refuses segments shorter than its window)
 };
 
 // error plumbing (gmg_api.hip)
@@ -175,6 +176,8 @@ int gmg_launch_seg_partial(const gmg_model *m, const gmg_reads *r, const gmg_seg
                            double *d_out, hipStream_t s);
 int gmg_launch_all_frame(const gmg_model *m, const gmg_reads *r, const gmg_segments *sg,
                          const uint32_t *d_prefix, const int32_t *d_frame, double *d_af, hipStream_t s);
+int gmg_launch_fixed(const gmg_fixed_model *m, const gmg_reads *r, const gmg_segments *sg, int lo, int hi,
+                     double *d_out, hipStream_t s);
 int gmg_launch_windows(const gmg_model *m, const uint8_t *d_windows, const int32_t *d_frames, uint64_t n,
                        float *d_dist4, double *d_prob, hipStream_t s);
 

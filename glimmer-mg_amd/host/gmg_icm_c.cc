@@ -148,3 +148,159 @@ extern "C" int  gmg_icm_device_model  (const gmg_icm * icm, const gmg_model * * 
    * out = icm -> model . Device_Model ();
    return  GMG_OK;
   }
+
+
+// ---------------------------------------------------------------------------
+// fixed-length ICMs
+// ---------------------------------------------------------------------------
+
+struct gmg_fixed_icm
+  {
+   Fixed_Length_ICM_t  scorer;
+   Fixed_Length_ICM_Training_t  * trained;     // NULL for a model that was read
+   gmg_fixed_icm  ()  : trained (NULL)  {}
+   ~ gmg_fixed_icm  ()  { delete  trained; }
+  };
+
+//  the scorer of a trained model: its binary bytes read back through the same path as a file (Try_Input)
+static bool  Load_Trained  (gmg_fixed_icm * h, string & err)
+  {
+   char  * buf = NULL;
+   size_t  len = 0;
+   FILE  * mem = open_memstream (& buf, & len);
+   if  (mem == NULL)
+       { err = "gmg_fixed_icm_train: open_memstream failed";  return  false; }
+   h -> trained -> Output (mem, true);
+   fclose (mem);
+   FILE  * in = fmemopen (buf, len, "rb");
+   bool  ok = (in != NULL) && h -> scorer . Try_Input (in, err);
+   if  (in != NULL)
+       fclose (in);
+   free (buf);
+   return  ok;
+  }
+
+extern "C" int  gmg_fixed_icm_read  (const char * path, gmg_fixed_icm * * out)
+  {
+   if  (path == NULL || out == NULL)
+       return  gmg_set_error (GMG_EINVAL, "gmg_fixed_icm_read: NULL argument");
+   gmg_fixed_icm  * h = new (nothrow) gmg_fixed_icm ();
+   if  (h == NULL)
+       return  gmg_set_error (GMG_ENOMEM, "gmg_fixed_icm_read: out of memory");
+   string  err;
+   if  (! h -> scorer . Try_Read (path, err))
+       {
+        delete  h;
+        return  gmg_set_error (GMG_EBADMODEL, "%s", err . c_str ());
+       }
+   * out = h;
+   return  GMG_OK;
+  }
+
+extern "C" int  gmg_fixed_icm_train
+    (const char * const * strings, int n, int max_depth, int special, const int * perm, gmg_fixed_icm * * out)
+  {
+   if  (out == NULL || strings == NULL || n < 1 || max_depth < 0 || max_depth > 12)
+       return  gmg_set_error (GMG_EINVAL, "gmg_fixed_icm_train: bad argument");
+   const int  len = int (strlen (strings [0]));
+   for  (int i = 0;  i < n;  i ++)
+     if  (strings [i] == NULL || int (strlen (strings [i])) != len)
+         return  gmg_set_error (GMG_EINVAL, "gmg_fixed_icm_train: string #%d has a length different from string #0 length = %d", i, len);
+   if  (len < 1 || len > 32)
+       return  gmg_set_error (GMG_EBADMODEL, "gmg_fixed_icm_train: length %d outside 1 .. 32", len);
+   if  (perm != NULL)
+     {
+      vector <bool>  seen (len, false);
+      for  (int i = 0;  i < len;  i ++)
+        {
+         if  (perm [i] < 0 || perm [i] >= len || seen [perm [i]])
+             return  gmg_set_error (GMG_EBADMODEL, "gmg_fixed_icm_train: the permutation is not a bijection of 0..%d", len - 1);
+         seen [perm [i]] = true;
+        }
+     }
+   //  Train_Model permutes its strings in place: train on copies
+   vector <string>  copies (strings, strings + n);
+   vector <char *>  data (n);
+   for  (int i = 0;  i < n;  i ++)
+     data [i] = & copies [i] [0];
+   gmg_fixed_icm  * h = new (nothrow) gmg_fixed_icm ();
+   if  (h == NULL)
+       return  gmg_set_error (GMG_ENOMEM, "gmg_fixed_icm_train: out of memory");
+   h -> trained = new Fixed_Length_ICM_Training_t (len, max_depth, special, const_cast <int *> (perm));
+   string  err;
+   if  (! h -> trained -> Try_Train_Model (data, err) || ! Load_Trained (h, err))
+       {
+        delete  h;
+        return  gmg_set_error (GMG_EHIP, "%s", err . c_str ());
+       }
+   * out = h;
+   return  GMG_OK;
+  }
+
+extern "C" int  gmg_fixed_icm_write  (gmg_fixed_icm * icm, const char * path, int binary)
+  {
+   if  (icm == NULL || path == NULL)
+       return  gmg_set_error (GMG_EINVAL, "gmg_fixed_icm_write: NULL argument");
+   if  (icm -> trained == NULL)
+       return  gmg_set_error (GMG_EINVAL, "gmg_fixed_icm_write: only a model trained here can be written (Fixed_Length_ICM_t has no Output)");
+   FILE  * fp = fopen (path, "wb");
+   if  (fp == NULL)
+       return  gmg_set_error (GMG_EINVAL, "ERROR:  Could not open file  %s  errno = %d", path, errno);
+   icm -> trained -> Output (fp, binary != 0);
+   if  (fclose (fp) != 0)
+       return  gmg_set_error (GMG_EINVAL, "gmg_fixed_icm_write: write to %s failed", path);
+   return  GMG_OK;
+  }
+
+extern "C" int  gmg_fixed_icm_params
+    (const gmg_fixed_icm * icm, int * length, int * max_depth, int * special, int * type, int * perm)
+  {
+   if  (icm == NULL)
+       return  gmg_set_error (GMG_EINVAL, "gmg_fixed_icm_params: NULL model");
+   Fixed_Length_ICM_t  & m = const_cast <Fixed_Length_ICM_t &> (icm -> scorer);
+   if  (length)  * length = m . getModelLength ();
+   if  (max_depth)  * max_depth = m . Get_Max_Depth ();
+   if  (special)  * special = m . getSpecialPosition ();
+   if  (type)  * type = m . getModelType ();
+   if  (perm && m . Get_Permutation () != NULL)
+       memcpy (perm, m . Get_Permutation (), m . getModelLength () * sizeof (int));
+   return  GMG_OK;
+  }
+
+extern "C" int  gmg_fixed_icm_score
+    (gmg_fixed_icm * icm, const char * const * strings, int n, int lo, int hi, double * out)
+  {
+   if  (icm == NULL || (n > 0 && (strings == NULL || out == NULL)) || n < 0)
+       return  gmg_set_error (GMG_EINVAL, "gmg_fixed_icm_score: bad argument");
+   for  (int k = 0;  k < n;  k ++)
+     if  (strings [k] == NULL)
+         return  gmg_set_error (GMG_EINVAL, "gmg_fixed_icm_score: string %d is NULL", k);
+   //  the reference's checks first (host only), so that their messages do not depend on a device
+   string  err;
+   if  (lo < 0 || icm -> scorer . getModelLength () < hi || hi < lo)
+       return  gmg_set_error (GMG_EINVAL, "ERROR:  Bad range  lo = %d  hi = %d  in subrange_score", lo, hi);
+   for  (int k = 0;  k < n;  k ++)
+     if  (! icm -> scorer . Check_Window (strings [k], lo, hi, err))
+         return  gmg_set_error (err . find ("too short") != string :: npos ? GMG_ERANGE : GMG_EINVAL, "%s", err . c_str ());
+   if  (gmg_device_count () <= 0)
+       return  gmg_set_error (GMG_ENODEV, "gmg_fixed_icm_score: no HIP device; there is no CPU fallback");
+   if  (! icm -> scorer . Try_Score_Windows (strings, n, lo, hi, out, err))
+       return  gmg_set_error (err . find ("too short") != string :: npos ? GMG_ERANGE : GMG_EINVAL, "%s", err . c_str ());
+   return  GMG_OK;
+  }
+
+extern "C" int  gmg_fixed_icm_device_model  (gmg_fixed_icm * icm, const gmg_fixed_model * * out)
+  {
+   if  (icm == NULL || out == NULL)
+       return  gmg_set_error (GMG_EINVAL, "gmg_fixed_icm_device_model: NULL argument");
+   if  (gmg_device_count () <= 0)
+       return  gmg_set_error (GMG_ENODEV, "gmg_fixed_icm_device_model: no HIP device; there is no CPU fallback");
+   * out = icm -> scorer . Device_Model ();
+   return  GMG_OK;
+  }
+
+extern "C" int  gmg_fixed_icm_free  (gmg_fixed_icm * icm)
+  {
+   delete  icm;
+   return  GMG_OK;
+  }

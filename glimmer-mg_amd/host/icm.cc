@@ -10,6 +10,7 @@
 //  work belongs on the batch entry points of include/gmg.h.
 
 #include "icm.hh"
+#include "icm_internal.hh"
 #include "../../include/gmg.h"
 
 #include <assert.h>
@@ -27,7 +28,8 @@ extern int  Verbose;   // src/Common/delcher.cc:20 in the reference; weak defaul
 // small helpers around the C ABI
 // ---------------------------------------------------------------------------
 
-namespace {
+//  shared with fixed_icm.cc (icm_internal.hh)
+namespace gmg_host {
 
 void  Device_Fatal  (const char * who)
   {
@@ -54,13 +56,21 @@ struct  Thread_Staging_t
    Thread_Staging_t  ()  : st (NULL)  {}
    ~ Thread_Staging_t  ()  { if  (st != NULL)  gmg_single_free (st); }
   };
-static gmg_single  * Thread_Staging  (void)
+gmg_single  * Thread_Staging  (void)
   {
    static thread_local Thread_Staging_t  mine;
    if  (mine . st == NULL && gmg_single_create (& mine . st) != GMG_OK)
        Device_Fatal ("gmg_single_create");
    return  mine . st;
   }
+
+}  // namespace gmg_host
+
+namespace {
+
+using gmg_host :: Device_Fatal;
+using gmg_host :: Ensure_Device;
+using gmg_host :: Thread_Staging;
 
 //  One string as a one-read batch in HBM, plus a device output buffer: the calling thread's gmg_single (persistent
 //  page-locked staging and device buffers: a call is one copy in, one launch, one copy out; nothing is allocated)

@@ -4,8 +4,9 @@
 //  Same public interface, constants, field names and error behaviour as the
 //  reference's  ICM_t  (src/ICM/icm.hh:26-84,106-180,303), so that code written
 //  against it (src/Glimmer/glimmer3.cc, glimmer-mg.cc, glimmer_base.cc,
-//  src/ICM/build-icm.cc) recompiles unchanged.  (src/ICM/score-fixed.cc does NOT: it also
-//  needs Fixed_Length_ICM_t, src/ICM/icm.hh:216-289, which is out of scope -- SURVEY 2, row 10.)  Everything that computes a
+//  src/ICM/build-icm.cc) recompiles unchanged -- and so do src/ICM/build-fixed.cc and
+//  src/ICM/score-fixed.cc, through the fixed-length classes below (Fixed_Length_ICM_t,
+//  Fixed_Length_ICM_Training_t, src/ICM/icm.hh:216-289).  Everything that computes a
 //  score goes through the extern "C" HIP layer declared in include/gmg.h;
 //  there is no CPU scoring path in this class.  Model I/O and the null-model
 //  builder are host code, as in the reference.
@@ -21,6 +22,7 @@
 #include <vector>
 
 struct gmg_model;   // include/gmg.h
+struct gmg_fixed_model;
 
 // ---- constants of src/ICM/icm.hh:21-80 (callers and the training code use them) ----
 #define  STORE_MUT_INFO  1
@@ -46,6 +48,10 @@ const double  PSEUDO_COUNT = 0.001;
 const int  SAMPLE_SIZE_BOUND = 400;
 
 #define  PARENT(x) ((int) ((x) - 1) / ALPHABET_SIZE)
+
+//  src/ICM/icm.hh:91-92
+enum  ICM_Model_t
+    {UNKNOWN_TYPE};
 
 
 //  src/ICM/icm.hh:106-113 (STORE_MUT_INFO = 1 layout, 24 bytes)
@@ -167,6 +173,121 @@ class  ICM_Training_t  :  public ICM_t
    bool  Try_Train_Model
        (const char * const * data, int string_ct, std::string & err);
   };
+
+
+//  src/ICM/icm.hh:216-255.  A fixed-length model of  length  L: sub-model i (0-based) is an ICM_t of model_len i+1,
+//  periodicity 1, that predicts base i of the window after Permute_String.  Score_Window / subrange_score are ONE
+//  gmg_fixed_score call each (include/gmg.h: the window, its permutation and all L descents on the device); the batch form
+//  Score_Windows is one call for all its strings.  Deviations from the reference: L must be 1..32 (a window of 2-bit codes
+//  fits one 64-bit register) and the permutation must be a bijection of 0..L-1 -- both are refused with a message and
+//  exit(EXIT_FAILURE) where the reference reads on (and has undefined behaviour); every sub-model must have the shape the
+//  training class writes (model_len i+1, periodicity 1).  Subscript maps every character to a base
+//  (tolower (Filter (ch)), '\0' included), so the only character error of Score_Window / subrange_score is the
+//  reference's "too short" check on the permuted window.
+class  Fixed_Length_ICM_t
+  {
+  private:
+   int  length;
+   int  max_depth;
+   int  special_position;
+   ICM_Model_t  model_type;
+   int  * permutation;
+   std::vector <ICM_t *> sub_model;
+
+  public:
+   Fixed_Length_ICM_t
+       (int len = 1, int sp = 0, int * perm = NULL, ICM_Model_t = UNKNOWN_TYPE);
+   ~ Fixed_Length_ICM_t
+       ();
+
+   int  Get_Length
+       (void)
+     { return  length; }
+   double  Score_Window
+       (char * w);
+
+   // Match MDD_t interface
+   int  getModelLength
+       (void)
+     { return  length; }
+   int  getModelType
+       (void)
+     { return  model_type; }
+   int  getSpecialPosition
+       (void)
+     { return  special_position; }
+   void  read
+       (const char * path);
+   double  subrange_score
+       (char * w, int lo, int hi);
+   double  score
+       (char * w)
+     { return  Score_Window (w); }
+
+   // ---- additions ---------------------------------------------------------
+   //  read without the exit: returns false and sets  err  (the message the reference would print)
+   bool  Try_Read
+       (const char * path, std::string & err);
+   //  the same on an open stream (the bytes of one model are consumed)
+   bool  Try_Input
+       (FILE * fp, std::string & err);
+   //  out [k] = subrange_score (strings [k], lo, hi) for k < n, in ONE device call.  Exits as subrange_score would at the first
+   //  string it would stop at; Try_Score_Windows returns false and sets  err  instead.
+   void  Score_Windows
+       (const char * const * strings, int n, int lo, int hi, double * out);
+   bool  Try_Score_Windows
+       (const char * const * strings, int n, int lo, int hi, double * out, std::string & err);
+   int  Get_Max_Depth  (void)  const  { return  max_depth; }
+   //  the permutation as read (identity when the model has none); NULL before read
+   const int *  Get_Permutation  (void)  const  { return  permutation; }
+   const ICM_t *  Get_Sub_Model  (int i)  const  { return  sub_model [i]; }
+   //  Device copy of all L sub-models and the permutation (uploaded on first use, dropped by read)
+   const gmg_fixed_model *  Device_Model  (void)  const;
+   //  the reference's "too short" check of subrange_score (w, lo, hi) alone: false and its message when it would stop there
+   bool  Check_Window  (const char * w, int lo, int hi, std::string & err)  const;
+
+  private:
+   mutable gmg_fixed_model  * dev_fixed;
+   void  Clear  (void);
+  };
+
+
+//  src/ICM/icm.hh:258-289.  Train_Model permutes the caller's strings in place, as the reference does, then trains
+//  sub-model i (1 <= i <= length) as ICM_Training_t (i, min (i - 1, max_depth), 1) on the length-i prefixes: the device
+//  counting of ICM_Training_t, L times.  Output / Write_Header write the reference's bytes (binary, and -t text).
+class  Fixed_Length_ICM_Training_t
+  {
+  private:
+   int  length;
+   int  max_depth;
+   int  special_position;
+   ICM_Model_t  model_type;
+   int  * permutation;
+   std::vector <ICM_Training_t *> sub_model;
+
+  public:
+   Fixed_Length_ICM_Training_t
+       (int len, int md, int sp, int * perm, ICM_Model_t mt = UNKNOWN_TYPE);
+   ~ Fixed_Length_ICM_Training_t
+       ();
+   void  Output
+       (FILE * fp, bool binary_form);
+   void  Train_Model
+       (std::vector <char *> & data);
+   void  Write_Header
+       (FILE * fp, bool binary_form);
+
+   // ---- additions ---------------------------------------------------------
+   //  Train_Model without the exit: returns false and sets  err  when the device layer fails
+   bool  Try_Train_Model
+       (std::vector <char *> & data, std::string & err);
+  };
+
+
+void  Permute_Data
+    (std::vector <char *> & data, int * perm);
+void  Permute_String
+    (char * s, int * perm, int n);
 
 
 int  Subscript

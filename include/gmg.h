@@ -241,6 +241,27 @@ int gmg_all_frame_score(const gmg_model *gene, const gmg_reads *reads, const gmg
 int gmg_window_distrib(const gmg_model *m, const uint8_t *d_windows, const int32_t *d_frames,
                        uint64_t n_windows, float *d_dist4, double *d_prob, void *stream);
 
+/* ---- fixed-length ICMs: replaces Fixed_Length_ICM_t's scoring (src/ICM/icm.hh:216-255, icm.cc:1466-1645) -------------
+ * A fixed-length model of length L (1 <= L <= 32) is L sub-models; sub-model i (0-based) is an ICM_t of model_len i+1,
+ * periodicity 1, that predicts base i of the PERMUTED window from bases 0..i-1 of it.  gmg_fixed_model_upload takes the
+ * tables of sub-model i as gmg_model_upload would (mip[i][num_nodes[i]], prob4[i][num_nodes[i] * 4], depth model_depth[i]
+ * in [0, min(i, 12)]) and perm[L], which must be a bijection of 0..L-1 (GMG_EBADMODEL otherwise: the reference does not
+ * check, an invalid permutation is undefined behaviour there). */
+typedef struct gmg_fixed_model gmg_fixed_model;
+int gmg_fixed_model_upload(int length, const int32_t *perm, const int16_t *const *mip, const float *const *prob4,
+                           const int *model_depth, const int *num_nodes, gmg_fixed_model **out);
+int gmg_fixed_model_free(gmg_fixed_model *m);
+/* length, the largest sub-model depth and the bytes of the flattened tables on the device (any pointer may be NULL) */
+int gmg_fixed_model_info(const gmg_fixed_model *m, int *length, int *max_depth, uint64_t *table_bytes);
+/* Fixed_Length_ICM_t::subrange_score (src/ICM/icm.cc:1565-1645) of every segment:
+ *   d_out[k] = sum_{i=lo}^{hi-1} FWP_i(perm(B_k[0..L)))
+ * with B_k the segment's buffer in its gmg_orient, P = perm(B) the window Permute_String makes (P[i] = B[perm[i]]) and FWP_i
+ * ICM_t::Full_Window_Prob of sub-model i on P[0..i].  The sum is double additions in i order from 0.0, as the reference's.
+ * Bases of a segment past L are ignored (strncpy (buff, w, length)); a segment shorter than L is GMG_ERANGE; lo == hi
+ * gives 0.0; 0 <= lo <= hi <= L (GMG_EINVAL otherwise).  Fixed_Length_ICM_t::Score_Window is lo = 0, hi = L. */
+int gmg_fixed_score(const gmg_fixed_model *m, const gmg_reads *reads, const gmg_segments *segs,
+                    int lo, int hi, double *d_out, void *stream);
+
 /* ---- Score_Orfs inner loop (src/Glimmer/glimmer3.cc:1275-1552) ------------------- */
 
 /* One Orf_t as Find_Orfs produced it (src/Common/gene.hh:101-139). */

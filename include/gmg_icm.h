@@ -36,6 +36,29 @@ int gmg_icm_tables(const gmg_icm *icm, int16_t *mip, float *prob4);
 /* device mirror of the tables: uploaded on first use, owned by the gmg_icm */
 int gmg_icm_device_model(const gmg_icm *icm, const gmg_model **out);
 
+/* ---- fixed-length ICMs (src/ICM/icm.hh:216-289) -------------------------------------------------------------------
+ * A gmg_fixed_icm owns one Fixed_Length_ICM_t (the scorer) and, when it was trained here, the Fixed_Length_ICM_Training_t
+ * that wrote it (for gmg_fixed_icm_write). */
+typedef struct gmg_fixed_icm gmg_fixed_icm;
+/* Fixed_Length_ICM_t::read without the exit (src/ICM/icm.cc:1502-1559): GMG_EBADMODEL with the reference's message for a bad
+ * version, and for what this library refuses: a length outside 1..32, a permutation that is not a bijection of 0..L-1 */
+int gmg_fixed_icm_read(const char *path, gmg_fixed_icm **out);
+/* build-fixed: Fixed_Length_ICM_Training_t (L, max_depth, special, perm) + Train_Model on n_strings NUL-terminated strings of
+ * length L = strlen(strings[0]) (the strings are copied: the caller's are not permuted); perm = NULL for none */
+int gmg_fixed_icm_train(const char *const *strings, int n_strings, int max_depth, int special_position, const int *perm,
+                        gmg_fixed_icm **out);
+/* Fixed_Length_ICM_Training_t::Output: binary != 0 the model file, 0 the -t text; GMG_EINVAL for a model that was read */
+int gmg_fixed_icm_write(gmg_fixed_icm *icm, const char *path, int binary);
+/* length, max_depth, special position, model type and the permutation (perm: room for 32 ints, or NULL) */
+int gmg_fixed_icm_params(const gmg_fixed_icm *icm, int *length, int *max_depth, int *special_position, int *model_type,
+                         int *perm);
+/* out[k] = Fixed_Length_ICM_t::subrange_score(strings[k], lo, hi) in ONE device call (Score_Windows); GMG_ERANGE with the
+ * reference's "too short" message for the first string it would stop at, GMG_EINVAL for a bad range */
+int gmg_fixed_icm_score(gmg_fixed_icm *icm, const char *const *strings, int n_strings, int lo, int hi, double *out);
+/* the device copy of all sub-models (gmg_fixed_score), owned by the gmg_fixed_icm */
+int gmg_fixed_icm_device_model(gmg_fixed_icm *icm, const gmg_fixed_model **out);
+int gmg_fixed_icm_free(gmg_fixed_icm *icm);
+
 #ifdef __cplusplus
 }
 #endif
