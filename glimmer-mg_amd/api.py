@@ -640,6 +640,85 @@ def score_reads_strings(models, reads):
     return out
 
 
+class TopHits:
+    """gmg_tophits: the best `top_hits` models of every read of `reads`, kept in HBM while a database of ICMs streams through in
+    batches (Phymm's raw matrix + glimmer-mg.py's parse_phymm / score_insert; include/gmg.h).  Keys are the %.4f text of a score as
+    an integer count of 1e-4 units."""
+
+    def __init__(self, reads, top_hits):
+        self.reads = reads                              # (the handle scores this batch: it must outlive the handle)
+        self.top_hits = int(top_hits)
+        self.h = C.c_void_p()
+        _ck(capi.lib().gmg_tophits_create(reads.h, self.top_hits, C.byref(self.h)))
+
+    @staticmethod
+    def _inf(informative, B):
+        if informative is None:
+            return None, None
+        inf = np.ascontiguousarray(informative, np.uint8)
+        assert len(inf) == B
+        return inf, _ptr(inf)
+
+    def update_sums(self, sums, first_model=0, informative=None, forward_only=False):
+        """gmg_tophits_update_sums on HOST sums float64 [B, n_reads, 2] (uploaded first)"""
+        sums = np.ascontiguousarray(sums, np.float64)
+        B = sums.shape[0]
+        buf = _DeviceBuffer.from_host(sums)
+        inf, p = self._inf(informative, B)
+        try:
+            _ck(capi.lib().gmg_tophits_update_sums(self.h, buf.ptr, B, int(first_model), p, int(bool(forward_only)), None))
+        finally:
+            buf.free()
+
+    def scores(self, models, first_model=0, informative=None, forward_only=False, return_sums=False):
+        """gmg_tophits_scores: the models scored on the device into the handle's scratch, then the update; return_sums: the
+        scratch copied back, float64 [B, n_reads, 2]"""
+        B = len(models)
+        arr = (C.c_void_p * max(B, 1))(*[m.device() for m in models])
+        inf, p = self._inf(informative, B)
+        d = C.c_void_p()
+        _ck(capi.lib().gmg_tophits_scores(self.h, arr, B, int(first_model), p, int(bool(forward_only)), None, C.byref(d)))
+        if return_sums:
+            out = np.empty(B * self.reads.n_reads * 2, np.float64)
+            if out.nbytes:
+                _ck(capi.lib().gmg_memcpy_d2h(_ptr(out), d, out.nbytes, None))
+                _ck(capi.lib().gmg_synchronize(None))
+            return out.reshape(B, self.reads.n_reads, 2)
+
+    def fetch(self):
+        """-> (keys int64 [n_reads, top_hits], models int32 [n_reads, top_hits]); an empty slot has model -1"""
+        n = self.reads.n_reads
+        keys = np.zeros((max(n, 1), self.top_hits), np.int64)
+        models = np.zeros((max(n, 1), self.top_hits), np.int32)
+        _ck(capi.lib().gmg_tophits_fetch(self.h, _ptr(keys), _ptr(models)))
+        return keys[:n], models[:n]
+
+    def format_rows(self, sums, forward_only=False):
+        """gmg_tophits_format_rows on HOST sums float64 [B, n_reads, 2] -> the B data-matrix lines (bytes)"""
+        sums = np.ascontiguousarray(sums, np.float64)
+        B = sums.shape[0]
+        buf = _DeviceBuffer.from_host(sums)
+        cap = max(B * self.reads.n_reads * capi.TOPHITS_MAX_FIELD, B, 1)
+        out = np.empty(cap, np.uint8)
+        size = C.c_size_t(cap)
+        try:
+            _ck(capi.lib().gmg_tophits_format_rows(self.h, buf.ptr, B, int(bool(forward_only)), _ptr(out), C.byref(size), None))
+        finally:
+            buf.free()
+        return out[:size.value].tobytes()
+
+    def close(self):
+        if self.h:
+            capi.lib().gmg_tophits_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def window_distrib(model, windows, frames):
     """Full_Window_Distrib / Full_Window_Prob (icm.cc:512-610).  windows: uint8 codes [n, model_len]
     -> (dist float32 [n,4], prob float64 [n])"""

@@ -40,6 +40,8 @@ class MgParams(C.Structure):
                 ("n_ignore_regions", C.c_int32), ("reserved2", C.c_int32), ("ignore_lo", C.c_void_p), ("ignore_hi", C.c_void_p)]
 
 
+TOPHITS_MAX_FIELD = 19                      # GMG_TOPHITS_MAX_FIELD (include/gmg.h)
+
 PROTOTYPES = {
     # include/gmg.h
     "gmg_init": (i32, [i32]),
@@ -123,6 +125,12 @@ PROTOTYPES = {
     "gmg_fixed_model_free": (i32, [vp]),
     "gmg_fixed_model_info": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(u64)]),
     "gmg_fixed_score": (i32, [vp, vp, vp, i32, i32, vp, vp]),
+    "gmg_tophits_create": (i32, [vp, i32, C.POINTER(vp)]),
+    "gmg_tophits_free": (i32, [vp]),
+    "gmg_tophits_update_sums": (i32, [vp, vp, i32, i32, vp, i32, vp]),
+    "gmg_tophits_scores": (i32, [vp, vp, i32, i32, vp, i32, vp, C.POINTER(vp)]),
+    "gmg_tophits_fetch": (i32, [vp, vp, vp]),
+    "gmg_tophits_format_rows": (i32, [vp, vp, i32, i32, vp, C.POINTER(C.c_size_t), vp]),
     "gmg_device_malloc": (i32, [C.POINTER(vp), C.c_size_t]),
     "gmg_device_free": (i32, [vp]),
     "gmg_memcpy_h2d": (i32, [vp, vp, C.c_size_t, vp]),

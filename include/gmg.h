@@ -544,6 +544,41 @@ int gmg_trainer_create(const gmg_reads *strings, int model_len, int model_depth,
 int gmg_trainer_level_counts(gmg_trainer *t, int level, const int16_t *mip_prev, int32_t *counts);
 int gmg_trainer_free(gmg_trainer *t);
 
+/* ---- Phymm's classification step: every read against a database of ICMs -------------------------------
+ * Glimmer-MG's pipeline classifies reads with Phymm first: scoreReadsGlim.pl scores every read and its reverse complement
+ * under every ICM of a database (simple-score, the values printed with %.4f) and writes the raw matrix -- per read the
+ * reverse strand's text only when it parses to a strictly greater number; glimmer-mg.py's parse_phymm then keeps the best
+ * top_hits informative models of every read with its score_insert.  A gmg_tophits handle keeps those slots in HBM while the
+ * database streams through in batches of B models ([B][n_reads][2] sums, as gmg_score_reads_strings writes them).
+ * Scores are compared as the printed text orders them: the key of a value is its %.4f digits as an integer count of 1e-4
+ * units (glibc's rounding: the exact binary value, ties to even).  A value that is not finite or whose magnitude is
+ * 2^52 / 10^4 or more has no key here: GMG_ERANGE (after which the slots are undefined). */
+#define GMG_TOPHITS_MAX 16
+/* the most bytes one field of gmg_tophits_format_rows takes: sign, 12 integer digits, '.', 4 decimals, separator */
+#define GMG_TOPHITS_MAX_FIELD 19
+typedef struct gmg_tophits gmg_tophits;
+/* empty slots for every read of `reads` (which must outlive the handle); top_hits 1 .. GMG_TOPHITS_MAX */
+int gmg_tophits_create(const gmg_reads *reads, int top_hits, gmg_tophits **out);
+int gmg_tophits_free(gmg_tophits *h);
+/* score_insert of models first_model .. first_model + B - 1 (in that order) for every read: d_sums (device) [B][n_reads][2];
+ * informative (HOST, B entries; NULL = all) skips the models whose entry is 0; forward_only != 0 takes [..][0] alone (the
+ * script's -f).  The first top_hits models fill the empty slots in arrival order, unsorted; a later one goes in at the first
+ * slot it strictly beats, the slots behind move down.  Synchronises `stream`. */
+int gmg_tophits_update_sums(gmg_tophits *h, const double *d_sums, int B, int first_model, const uint8_t *informative,
+                            int forward_only, void *stream);
+/* gmg_score_reads_strings of the B models into a scratch buffer the handle owns (and reuses), then gmg_tophits_update_sums;
+ * *d_sums_out (may be NULL) = that buffer, valid until the next call on the handle */
+int gmg_tophits_scores(gmg_tophits *h, const gmg_model *const *models, int B, int first_model, const uint8_t *informative,
+                       int forward_only, void *stream, const double **d_sums_out);
+/* the slots (HOST, [n_reads][top_hits]): keys (the %.4f value x 10^4) and model indices; an empty slot has model -1 */
+int gmg_tophits_fetch(const gmg_tophits *h, int64_t *keys, int32_t *models);
+/* The B data-matrix lines of the raw file for d_sums (device, [B][n_reads][2]): per model one line, per read the winning
+ * strand's %.4f text, tab-separated, ending in a newline -- formatted on the device.  *bytes: in = capacity of host_out, out =
+ * the length of the lines; host_out NULL only asks for that length, a smaller capacity is GMG_ERANGE.  B * n_reads *
+ * GMG_TOPHITS_MAX_FIELD bytes (B without reads) always suffice.  Synchronises `stream`. */
+int gmg_tophits_format_rows(gmg_tophits *h, const double *d_sums, int B, int forward_only, char *host_out, size_t *bytes,
+                            void *stream);
+
 /* ---- device memory helpers (for callers without their own allocator) -------- */
 int gmg_device_malloc(void **d_ptr, size_t bytes);
 int gmg_device_free(void *d_ptr);
