@@ -463,13 +463,6 @@ struct FaCopyLane {
 };
 FaCopyLane &copy_lane() { static FaCopyLane *c = new FaCopyLane(); return *c; }
 
-struct DevFree {                                       // temporaries, from the library's cache of device blocks
-    std::vector<void *> v;
-    hipStream_t st = nullptr;
-    ~DevFree() { (void)hipStreamSynchronize(st); for (void *p : v) gmg_pool_release(p); }
-    template <class T> hipError_t alloc(T **p, size_t bytes) { hipError_t e = gmg_pool_alloc((void **)p, bytes); if (e == hipSuccess) v.push_back(*p); return e; }
-};
-
 }  // namespace
 
 extern "C" int gmg_fasta_free(gmg_fasta *f)
@@ -528,7 +521,8 @@ extern "C" int gmg_fasta_ingest_on(const char *bytes, uint64_t n_bytes, gmg_read
     uint64_t *d_off = nullptr;
     struct BufGuard { uint32_t *&p; ~BufGuard() { if (p) gmg_pool_release(p); } } alloc_guard = {d_alloc};   // until the reads own it
     struct OffGuard { uint64_t *&p; ~OffGuard() { if (p) gmg_pool_release(p); } } off_guard = {d_off};       // until then it is ours
-    DevFree dev;
+    GmgScratch dev;                                     // temporaries: back to the cache once the stream has drained
+    dev.wait = GmgScratch::STREAM;
     dev.st = st;
     uint8_t *d_bytes = nullptr, *d_func = nullptr, *d_bstate = nullptr;
     FaSumm *d_summ = nullptr;

@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
 #include "../../include/gmg.h"
 
 #define GMG_MAX_MODEL_LEN 32      // context of W-1 <= 31 bases fits one 64-bit register
@@ -152,6 +153,43 @@ void gmg_ingest_trim(void);                       // gmg_ingest.hip: frees its c
 hipError_t gmg_pool_alloc(void **out, size_t bytes);
 void gmg_pool_release(void *p);
 void gmg_pool_release_after(void *p, hipStream_t s);   // ... once the work queued on s so far is done
+
+// The blocks one call holds, by scope: whatever has not been released early or detached (handed to a result that outlives the
+// call) goes back to the cache when the holder ends -- behind a wait for the stream or the whole device where work that uses
+// the blocks may still be queued.
+struct __attribute__((visibility("hidden"))) GmgScratch {   // (hidden: no weak symbols of it among the library's exports)
+    enum Wait { NONE, STREAM, DEVICE };
+    Wait wait = NONE;
+    hipStream_t st = nullptr;
+    std::vector<void *> v;
+    GmgScratch() {}
+    GmgScratch(const GmgScratch &) = delete;
+    GmgScratch &operator=(const GmgScratch &) = delete;
+    ~GmgScratch()
+    {
+        if (wait == STREAM) (void)hipStreamSynchronize(st);
+        else if (wait == DEVICE) (void)hipDeviceSynchronize();
+        for (void *p : v) gmg_pool_release(p);
+    }
+    template <class T> hipError_t alloc(T **p, size_t bytes)
+    {
+        const hipError_t e = gmg_pool_alloc((void **)p, bytes);
+        if (e == hipSuccess) v.push_back(*p);
+        return e;
+    }
+    template <class T> void detach(T *p)                // the block is someone else's from here on
+    {
+        for (size_t k = 0; k < v.size(); k++)
+            if (v[k] == (void *)p) { v[k] = v.back(); v.pop_back(); return; }
+    }
+    template <class T> void release(T *&p)              // back to the cache now (nothing queued may still use it)
+    {
+        if (!p) return;
+        detach(p);
+        gmg_pool_release(p);
+        p = nullptr;
+    }
+};
 
 // kernel launchers (gmg_kernels.hip)
 int gmg_launch_tile_read(const uint64_t *d_off, uint64_t n_reads, uint64_t n_tiles, uint32_t *d_tile_read,
