@@ -419,7 +419,8 @@ OPTION_SETS = [
 
 
 @pytest.mark.parametrize("mode", ["classes", "one_icm"])
-@pytest.mark.parametrize("opts", OPTION_SETS, ids=["_".join(o[:2]).replace(",", "").replace("/", "") [:24] for o in OPTION_SETS])
+# (ids name a file argument by its base name: they must not depend on where the repository is checked out)
+@pytest.mark.parametrize("opts", OPTION_SETS, ids=["_".join(os.path.basename(x) for x in o[:2]).replace(",", "")[:24] for o in OPTION_SETS])
 def test_driver_options_against_the_reference_run_here(gpu, tmp_path, opts, mode):
     """every glimmer-mg option that changes what is scored or how the events are weighed (-Z / -z stop codons for all reads, -b RBS
     matrix, -f feature file, -g, -o, -u, -s, -i) with -c and with -m: the reference binary run in the test against glimmer-mg_gpu on

@@ -193,7 +193,8 @@ G3_OPTION_SETS = [
 ]       # (the reference's getopt string gives -f an argument it never reads and -F none although it reads one: -F cannot be used)
 
 
-@pytest.mark.parametrize("opts", G3_OPTION_SETS, ids=["_".join(o[:2]).replace(",", "").replace("/", "")[:20] for o in G3_OPTION_SETS])
+# (ids name a file argument by its base name: they must not depend on where the repository is checked out)
+@pytest.mark.parametrize("opts", G3_OPTION_SETS, ids=["_".join(os.path.basename(x) for x in o[:2]).replace(",", "")[:20] for o in G3_OPTION_SETS])
 def test_glimmer3_gpu_options_against_the_reference_run_here(gpu, tmp_path, opts):
     """every glimmer3 option that changes the ORFs, the scoring or the weights of the DP (start / stop codon sets, GC, first-start rule,
     lengths, overlap, Ignore_Score_Len, threshold, RBS matrix, feature file, prior): oracle/_ref/glimmer3 run in the test against
