@@ -187,6 +187,107 @@ class Icm:
             pass
 
 
+class _SetModel:
+    """member k of a ModelSet: usable wherever an Icm's device model is (the set owns it)"""
+
+    def __init__(self, owner, handle):
+        self.owner, self.h = owner, handle
+
+    def device(self):
+        if not self.owner.h:
+            raise GmgError(-1, "the ModelSet of this model is closed")
+        return self.h
+
+
+class ModelSet:
+    """gmg_model_set: the raw bytes of many binary .icm files parsed and flattened on the device, in one block.
+    ModelSet.load queues the work on `stream` and returns; finish() waits and raises GmgError (with .bad_file) when the device
+    refused a file; model(k) is valid after finish()."""
+
+    def __init__(self, handle, blobs, n):
+        self.h, self._blobs, self.n, self._done = handle, blobs, n, False
+
+    @classmethod
+    def load(cls, list_of_bytes, stream=None):
+        blobs = [np.frombuffer(bytes(b), np.uint8) if len(b) else np.zeros(0, np.uint8) for b in list_of_bytes]     # kept until finish()
+        n = len(blobs)
+        ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in blobs])
+        sizes = (C.c_uint64 * max(n, 1))(*[b.size for b in blobs])
+        h = C.c_void_p()
+        _ck(capi.lib().gmg_model_set_load(ptrs, sizes, n, C.byref(h), stream))
+        return cls(h, blobs, n)
+
+    def finish(self):
+        bad = C.c_int(-1)
+        rc = capi.lib().gmg_model_set_finish(self.h, C.byref(bad))
+        self._blobs = None
+        if rc != 0:
+            err = GmgError(rc, capi.lib().gmg_last_error().decode("utf-8", "replace"))
+            err.bad_file = bad.value
+            raise err
+        self._done = True
+        return self
+
+    def model(self, k):
+        if not self._done:
+            self.finish()
+        h = capi.lib().gmg_model_set_model(self.h, int(k))
+        if not h:
+            raise GmgError(-1, capi.lib().gmg_last_error().decode("utf-8", "replace"))
+        return _SetModel(self, C.c_void_p(h))
+
+    def __len__(self):
+        return self.n
+
+    def close(self):
+        if self.h:
+            capi.lib().gmg_model_set_free(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def icm_bytes_info(data):
+    """gmg_icm_bytes_info: (model_len, model_depth, periodicity, num_nodes, blob_bytes) of a binary .icm's bytes (host only)"""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    w, d, p, n, b = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_uint64()
+    _ck(capi.lib().gmg_icm_bytes_info(buf.ctypes.data if buf.size else None, buf.size, C.byref(w), C.byref(d), C.byref(p), C.byref(n), C.byref(b)))
+    return w.value, d.value, p.value, n.value, b.value
+
+
+def model_info(m):
+    """gmg_model_info of an Icm's or a ModelSet member's device model: (model_len, model_depth, periodicity, num_nodes)"""
+    w, d, p, n = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    _ck(capi.lib().gmg_model_info(m.device(), C.byref(w), C.byref(d), C.byref(p), C.byref(n)))
+    return w.value, d.value, p.value, n.value
+
+
+def model_blob(m):
+    """gmg_model_blob: the device tables of a model as bytes, in gmg_model_upload's layout"""
+    size = C.c_size_t(0)
+    _ck(capi.lib().gmg_model_blob(m.device(), None, C.byref(size)))
+    out = np.empty(size.value, np.uint8)
+    _ck(capi.lib().gmg_model_blob(m.device(), _ptr(out), C.byref(size)))
+    return out.tobytes()
+
+
+def model_value_stats(m):
+    """gmg_model_value_stats: (min_exp, max_exp, odd_values)"""
+    lo, hi, odd = C.c_int(), C.c_int(), C.c_int()
+    _ck(capi.lib().gmg_model_value_stats(m.device(), C.byref(lo), C.byref(hi), C.byref(odd)))
+    return lo.value, hi.value, odd.value
+
+
 class NullSet:
     """gmg_null_set: (3,2,3) null models side by side on the device (glimmer-mg -c: Indep_Model per read)"""
 

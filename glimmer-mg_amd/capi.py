@@ -60,6 +60,13 @@ PROTOTYPES = {
     "gmg_model_upload": (i32, [vp, vp, i32, i32, i32, i32, C.POINTER(vp)]),
     "gmg_model_free": (i32, [vp]),
     "gmg_model_info": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+    "gmg_icm_bytes_info": (i32, [vp, u64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(u64)]),
+    "gmg_model_set_load": (i32, [vp, vp, i32, C.POINTER(vp), vp]),
+    "gmg_model_set_finish": (i32, [vp, C.POINTER(i32)]),
+    "gmg_model_set_model": (vp, [vp, i32]),
+    "gmg_model_set_free": (i32, [vp]),
+    "gmg_model_blob": (i32, [vp, vp, C.POINTER(C.c_size_t)]),
+    "gmg_model_value_stats": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     "gmg_reads_upload": (i32, [vp, vp, u64, C.POINTER(vp)]),
     "gmg_reads_wrap_device": (i32, [vp, vp, u64, u64, C.POINTER(vp)]),
     "gmg_reads_free": (i32, [vp]),

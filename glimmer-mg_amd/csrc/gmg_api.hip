@@ -250,6 +250,53 @@ static float dense_part_entry(const int16_t *mip, const float *prob, int W, int 
 
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Where the tables of one model lie inside its device blob, and what the shape allows: the one place that knows (gmg_model_upload
+// fills such a blob on the host, gmg_model_set_load on the device).  The shape has passed gmg_model_upload's checks.
+void gmg_model_layout(int W, int D, int P, int N, GmgModelLayout *out)
+{
+    GmgModelLayout &l = *out;
+    size_t need = 0, pw = 1;
+    for (int k = 0; k <= D; k++) { need += pw; pw *= 4; }
+    const size_t PN = (size_t)P * N;
+    l.fast = (W <= GMG_FAST_MAX_LEN && D <= GMG_FAST_MAX_DEPTH);
+    l.dense = (W <= GMG_DENSE_MAX_LEN);
+    l.n_internal = (pw / 4 - 1) / 3;                         // (4^D - 1) / 3
+    l.ctot = need;                                           // (4^(D+1) - 1) / 3
+    l.cstride = align_up(l.n_internal ? l.n_internal : 1, 16);
+    l.n_leaves = pw / 4;                                     // 4^D
+    l.n_dense = l.dense ? ((size_t)1 << (2 * W)) : 0;
+    l.n_part = l.dense ? (l.n_dense - 4) / 3 : 0;            // sum_{j<W-1} 4^(j+1)
+    l.o_mip = 0;
+    l.o_prob = align_up(l.o_mip + PN, 256);
+    l.o_cshift = align_up(l.o_prob + PN * 16, 256);
+    l.o_crow = align_up(l.o_cshift + (l.fast ? P * l.cstride : 0), 256);
+    l.o_chalf = align_up(l.o_crow + (l.fast ? (size_t)P * l.ctot * 16 + 16 : 0), 256);   // + one all-zero row
+    l.o_dense = align_up(l.o_chalf + (l.fast ? (size_t)P * l.n_leaves * 16 : 0), 256);
+    l.o_part = align_up(l.o_dense + (size_t)P * l.n_dense * 4, 256);
+    l.total = align_up(l.o_part + (size_t)P * l.n_part * 4 + 4, 256);
+}
+
+// The device view of a model whose blob (laid out as above) starts at d_blob.
+void gmg_model_bind(gmg_model *m, void *d_blob, int W, int D, int P, int N, const GmgModelLayout &l)
+{
+    unsigned char *d = (unsigned char *)d_blob;
+    m->d_blob = d_blob;
+    m->blob_bytes = l.total;
+    m->dev.W = W; m->dev.D = D; m->dev.P = P; m->dev.N = N;
+    m->dev.mip = (const int8_t *)(d + l.o_mip);
+    m->dev.prob = (const float *)(d + l.o_prob);
+    m->dev.cshift = l.fast ? (const uint8_t *)(d + l.o_cshift) : nullptr;
+    m->dev.crow = l.fast ? (const float *)(d + l.o_crow) : nullptr;
+    m->dev.chalf = l.fast ? (const float *)(d + l.o_chalf) : nullptr;
+    m->dev.cstride = (int)l.cstride;
+    m->dev.ctot = (int)l.ctot;
+    m->dev.has_fast = l.fast;
+    m->dev.dense = l.dense ? (const float *)(d + l.o_dense) : nullptr;
+    m->dev.dense_part = l.dense ? (const float *)(d + l.o_part) : nullptr;
+    m->dev.n_dense_part = (int)l.n_part;
+    m->dev.has_dense = l.dense;
+}
+
 extern "C" int gmg_model_upload(const int16_t *mip, const float *prob4, int W, int D, int P, int N,
                                 gmg_model **out)
 {
@@ -269,23 +316,13 @@ extern "C" int gmg_model_upload(const int16_t *mip, const float *prob4, int W, i
             return gmg_set_error(GMG_EBADMODEL, "gmg_model_upload: mut_info_pos %d at slot %zu outside [-2,%d]",
                                  (int)mip[i], i, W - 1);
 
-    const bool fast = (W <= GMG_FAST_MAX_LEN && D <= GMG_FAST_MAX_DEPTH);
-    const bool dense = (W <= GMG_DENSE_MAX_LEN);
-    const size_t n_internal = (size_t)((pw / 4 - 1) / 3);   // (4^D - 1) / 3
-    const size_t ctot = (size_t)need;                        // (4^(D+1) - 1) / 3
-    const size_t cstride = align_up(n_internal ? n_internal : 1, 16);
-    const size_t n_dense = dense ? ((size_t)1 << (2 * W)) : 0;
-    const size_t n_part = dense ? (n_dense - 4) / 3 : 0;     // sum_{j<W-1} 4^(j+1)
-
-    size_t o_mip = 0;
-    size_t o_prob = align_up(o_mip + PN, 256);
-    size_t o_cshift = align_up(o_prob + PN * 16, 256);
-    size_t o_crow = align_up(o_cshift + (fast ? P * cstride : 0), 256);
-    size_t o_chalf = align_up(o_crow + (fast ? (size_t)P * ctot * 16 + 16 : 0), 256);   // + one all-zero row
-    const size_t n_leaves = (size_t)(pw / 4);                // 4^D
-    size_t o_dense = align_up(o_chalf + (fast ? (size_t)P * n_leaves * 16 : 0), 256);
-    size_t o_part = align_up(o_dense + (size_t)P * n_dense * 4, 256);
-    size_t total = align_up(o_part + (size_t)P * n_part * 4 + 4, 256);
+    GmgModelLayout lay;
+    gmg_model_layout(W, D, P, N, &lay);
+    const bool fast = lay.fast, dense = lay.dense;
+    const size_t n_internal = lay.n_internal, ctot = lay.ctot, cstride = lay.cstride, n_dense = lay.n_dense, n_part = lay.n_part;
+    const size_t n_leaves = lay.n_leaves;
+    const size_t o_mip = lay.o_mip, o_prob = lay.o_prob, o_cshift = lay.o_cshift, o_crow = lay.o_crow, o_chalf = lay.o_chalf;
+    const size_t o_dense = lay.o_dense, o_part = lay.o_part, total = lay.total;
 
     std::vector<unsigned char> blob(total, 0);
     int8_t *h_mip = (int8_t *)(blob.data() + o_mip);
@@ -344,20 +381,7 @@ extern "C" int gmg_model_upload(const int16_t *mip, const float *prob4, int W, i
         if ((int)ex < m->min_exp) m->min_exp = (int)ex;
         if ((int)ex > m->max_exp) m->max_exp = (int)ex;
     }
-    unsigned char *d = (unsigned char *)m->d_blob;
-    m->dev.W = W; m->dev.D = D; m->dev.P = P; m->dev.N = N;
-    m->dev.mip = (const int8_t *)(d + o_mip);
-    m->dev.prob = (const float *)(d + o_prob);
-    m->dev.cshift = fast ? (const uint8_t *)(d + o_cshift) : nullptr;
-    m->dev.crow = fast ? (const float *)(d + o_crow) : nullptr;
-    m->dev.chalf = fast ? (const float *)(d + o_chalf) : nullptr;
-    m->dev.cstride = (int)cstride;
-    m->dev.ctot = (int)ctot;
-    m->dev.has_fast = fast;
-    m->dev.dense = dense ? (const float *)(d + o_dense) : nullptr;
-    m->dev.dense_part = dense ? (const float *)(d + o_part) : nullptr;
-    m->dev.n_dense_part = (int)n_part;
-    m->dev.has_dense = dense;
+    gmg_model_bind(m, m->d_blob, W, D, P, N, lay);
     *out = m;
     return GMG_OK;
 }

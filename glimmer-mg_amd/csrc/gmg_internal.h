@@ -52,6 +52,15 @@ struct gmg_model {
     size_t blob_bytes;
 };
 
+// Byte offsets of a model's tables inside its blob and the sizes they follow from (gmg_model_layout, gmg_api.hip)
+struct GmgModelLayout {
+    int fast, dense;             // has_fast (W <= 16, D <= 8), has_dense (W <= 6)
+    size_t n_internal, ctot, cstride, n_leaves, n_dense, n_part;
+    size_t o_mip, o_prob, o_cshift, o_crow, o_chalf, o_dense, o_part, total;
+};
+void gmg_model_layout(int W, int D, int P, int N, GmgModelLayout *out);
+void gmg_model_bind(gmg_model *m, void *d_blob, int W, int D, int P, int N, const GmgModelLayout &l);
+
 struct gmg_reads {
     const uint32_t *d_packed;
     const uint64_t *d_off;       // n_reads + 1

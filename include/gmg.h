@@ -114,6 +114,42 @@ int gmg_model_free(gmg_model *m);
 int gmg_model_info(const gmg_model *m, int *model_len, int *model_depth, int *periodicity,
                    int *num_nodes);
 
+/* ---- a batch of models from the bytes of their .icm files ---------------------- */
+/* The six header ints of a binary .icm, validated as ICM_t::Try_Input does (its messages in gmg_last_error(), status
+ * GMG_EBADMODEL).  Host only, no device needed.  blob_bytes (may be NULL): the size of the model's device tables; asking for it
+ * also applies gmg_model_upload's shape checks. */
+int gmg_icm_bytes_info(const void *bytes, uint64_t n_bytes, int *model_len, int *model_depth,
+                       int *periodicity, int *num_nodes, uint64_t *blob_bytes);
+
+/* n models in ONE device block, parsed and flattened on the device from the raw bytes of n binary .icm files.
+ *   gmg_model_set_load    reads the 24 header bytes of every file on the host (Try_Input's header messages, gmg_model_upload's
+ *                         shape checks: GMG_EBADMODEL), then queues on `stream` the copy of all files (a single copy when
+ *                         bytes[k+1] == bytes[k] + n_bytes[k] for every k) and the kernels; it does not wait.  bytes[k] must stay
+ *                         valid and unchanged until gmg_model_set_finish returns.
+ *   gmg_model_set_finish  waits for the stream's work and reads one status word per model.  GMG_EBADMODEL and *bad_file (may be
+ *                         NULL; -1 when all are good) for the first file the device refused, Try_Input's / gmg_model_upload's
+ *                         message in gmg_last_error().  One refusal is new: a record whose id does not exceed its predecessor's
+ *                         inside a sub-model (the reference's writer never produces one; gmg_icm_open reads such a file with the
+ *                         last record winning).  A refused set only serves gmg_model_set_free.
+ *   gmg_model_set_model   member k, valid after a successful finish; owned by the set -- never gmg_model_free.  It equals
+ *                         gmg_icm_open + gmg_icm_device_model on that file byte for byte.
+ *   gmg_model_set_free    does not block the host: the block goes back to the library's cache behind the load stream's work and
+ *                         whatever the null stream holds at the call; work on any other stream that uses the models must be
+ *                         complete.
+ * Pattern for a database: load batch k+1 on a second stream, score batch k, finish k+1, free k. */
+typedef struct gmg_model_set gmg_model_set;
+int gmg_model_set_load(const void *const *bytes, const uint64_t *n_bytes, int n_files,
+                       gmg_model_set **out, void *stream);
+int gmg_model_set_finish(gmg_model_set *s, int *bad_file);
+const gmg_model *gmg_model_set_model(const gmg_model_set *s, int k);
+int gmg_model_set_free(gmg_model_set *s);
+/* The device tables of a model as one blob, in gmg_model_upload's layout (tests, debugging): with dst NULL only *bytes is set,
+ * otherwise *bytes is the room at dst on entry and the blob's size on return. */
+int gmg_model_blob(const gmg_model *m, void *dst, size_t *bytes);
+/* What the values of a model allow (the smallest and largest exponent field among its non-zero values, whether any is positive,
+ * denormal, infinite or a NaN): the figures that choose between the reordered sums and the sequential kernels. */
+int gmg_model_value_stats(const gmg_model *m, int *min_exp, int *max_exp, int *odd_values);
+
 /* ---- reads ------------------------------------------------------------------ */
 
 int gmg_reads_upload(const uint32_t *packed2bit, const uint64_t *base_offsets, uint64_t n_reads,

@@ -8,7 +8,12 @@
 //  The models stream through the device in batches (gmg_tophits_scores: the scores and the per-read slots stay in HBM); the
 //  matrix lines are formatted on the device (gmg_tophits_format_rows).
 //
-//  usage: phymm_gpu [-f] [-i ignore_file] [-s suffix] [-t top_hits] [--informative FILE] [--no-matrix] [--batch-models B] <reads.fa>
+//  The ICM files themselves are parsed on the device too (gmg_model_set_load): a reader thread fills one of two page-locked
+//  buffers with the raw bytes of the next batch's files while the device scores the current one, and the load of that next batch
+//  is queued on a second stream before the scoring starts.  --host-load reads every model with gmg_icm_open instead (the
+//  cross-check; the output files are the same bytes).
+//
+//  usage: phymm_gpu [-f] [-i ignore_file] [-s suffix] [-t top_hits] [--informative FILE] [--no-matrix] [--batch-models B] [--host-load] <reads.fa>
 //
 //  Inputs whose outcome in the scripts is unknown or accidental are refused with a message (exit status 1): a record with an
 //  empty sequence, two records with one read ID, a header without an ID, fewer informative models than top_hits, an ICM path
@@ -18,15 +23,19 @@
 #include "../include/gmg_icm.h"
 
 #include <dirent.h>
+#include <errno.h>
+#include <fcntl.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <sys/stat.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <set>
 #include <string>
+#include <thread>
 #include <unordered_set>
 #include <vector>
 
@@ -34,7 +43,7 @@ namespace {
 
 const char *kUsage =
     "usage: phymm_gpu [-f] [-i ignore_file] [-s suffix] [-t top_hits] [--informative FILE] [--no-matrix] [--batch-models B] "
-    "<reads.fa>\n"
+    "[--host-load] <reads.fa>\n"
     "  run in the directory that holds .genomeData\n"
     "  -f                 score the forward strand only\n"
     "  -i FILE            ICMs to leave out: strain directories or full paths, one per line\n"
@@ -42,7 +51,8 @@ const char *kUsage =
     "  -t N               genomes per read in the class file, 1..16 (default 3)\n"
     "  --informative FILE the genomes (<dir>|<file stem>) that may classify a read (default: all)\n"
     "  --no-matrix        do not write rawPhymmOutput_<prefix>.txt\n"
-    "  --batch-models B   models per device batch (default 64)\n";
+    "  --batch-models B   models per device batch (default 64)\n"
+    "  --host-load        read every ICM on the host (gmg_icm_open) instead of parsing the files on the device\n";
 
 [[noreturn]] void Die(const char *fmt, const char *a = "", const char *b = "")
 {
@@ -111,11 +121,46 @@ std::string GenomeName(const std::string &path)
     return dir + "|" + file.substr(0, file.find('.'));
 }
 
+// The files of one batch, back to back in a page-locked buffer.  Fill() is all the reader thread runs: open / read / close, no
+// call into the library.  While a Fill() runs, the main thread touches nothing of that FileBatch (which models a batch holds is
+// computed from the batch's number, not kept here); the thread's join() hands it back.
+struct FileBatch {
+    unsigned char *buf = nullptr;
+    std::vector<const void *> ptr;
+    std::vector<uint64_t> size;
+    std::string error;                                  // what went wrong in Fill(), for the main thread to die with
+
+    void Fill(const std::vector<std::string> &paths, const std::vector<uint64_t> &sizes, size_t first, int nb)
+    {
+        ptr.assign(nb, nullptr);
+        size.assign(nb, 0);
+        error.clear();
+        size_t at = 0;
+        for (int k = 0; k < nb; k++) {
+            const std::string &path = paths[first + k];
+            const uint64_t want = sizes[first + k];
+            const int fd = open(path.c_str(), O_RDONLY);
+            if (fd < 0) { error = "Could not open file  " + path + "  errno = " + std::to_string(errno); return; }
+            uint64_t got = 0;
+            while (got < want) {
+                const ssize_t n = read(fd, buf + at + got, want - got);
+                if (n < 0 && errno == EINTR) continue;
+                if (n <= 0) break;
+                got += (uint64_t)n;
+            }
+            close(fd);
+            ptr[k] = buf + at;
+            size[k] = got;                              // (a file that shrank since stat(): the parser sees what is there)
+            at += want;
+        }
+    }
+};
+
 }  // namespace
 
 int main(int argc, char *argv[])
 {
-    bool forward_only = false, no_matrix = false;
+    bool forward_only = false, no_matrix = false, host_load = false;
     const char *ignore_file = nullptr, *informative_file = nullptr, *reads_file = nullptr;
     std::string suffix = "icm";
     int top_hits = 3, batch = 64;
@@ -132,6 +177,7 @@ int main(int argc, char *argv[])
         else if (a == "--informative") informative_file = value();
         else if (a == "--no-matrix") no_matrix = true;
         else if (a == "--batch-models") batch = atoi(value());
+        else if (a == "--host-load") host_load = true;
         else if (a == "-h" || a == "--help") { fputs(kUsage, stdout); return 0; }
         else if (a.size() > 1 && a[0] == '-') { fprintf(stderr, "ERROR:  unknown option %s\n%s", a.c_str(), kUsage); return EXIT_FAILURE; }
         else if (!reads_file) reads_file = argv[i];
@@ -250,14 +296,9 @@ int main(int argc, char *argv[])
         text.resize((size_t)B * n_reads * GMG_TOPHITS_MAX_FIELD);
         Check(gmg_host_register(text.data(), text.size()), "gmg_host_register");
     }
-    for (size_t first = 0; first < kept.size(); first += (size_t)B) {
-        const int nb = (int)std::min<size_t>((size_t)B, kept.size() - first);
-        std::vector<gmg_icm *> icm(nb);
-        std::vector<const gmg_model *> dev(nb);
-        for (int k = 0; k < nb; k++) {
-            if (gmg_icm_open(kept[first + k].c_str(), &icm[k]) != GMG_OK) Die("%s: %s", kept[first + k].c_str(), gmg_last_error());
-            Check(gmg_icm_device_model(icm[k], &dev[k]), "gmg_icm_device_model");
-        }
+    // one batch scored and its matrix lines written
+    auto score_batch = [&](const std::vector<const gmg_model *> &dev, size_t first) {
+        const int nb = (int)dev.size();
         const double *d_sums = nullptr;
         Check(gmg_tophits_scores(th, dev.data(), nb, (int)first, informative.data() + first, forward_only, nullptr, &d_sums),
               "gmg_tophits_scores");
@@ -266,7 +307,91 @@ int main(int argc, char *argv[])
             Check(gmg_tophits_format_rows(th, d_sums, nb, forward_only, text.data(), &n, nullptr), "gmg_tophits_format_rows");
             if (fwrite(text.data(), 1, n, raw) != n) Die("write error on %s", raw_name.c_str());
         }
-        for (int k = 0; k < nb; k++) gmg_icm_free(icm[k]);
+    };
+    if (host_load) {
+        for (size_t first = 0; first < kept.size(); first += (size_t)B) {
+            const int nb = (int)std::min<size_t>((size_t)B, kept.size() - first);
+            std::vector<gmg_icm *> icm(nb);
+            std::vector<const gmg_model *> dev(nb);
+            for (int k = 0; k < nb; k++) {
+                if (gmg_icm_open(kept[first + k].c_str(), &icm[k]) != GMG_OK) Die("%s: %s", kept[first + k].c_str(), gmg_last_error());
+                Check(gmg_icm_device_model(icm[k], &dev[k]), "gmg_icm_device_model");
+            }
+            score_batch(dev, first);
+            for (int k = 0; k < nb; k++) gmg_icm_free(icm[k]);
+        }
+    } else {
+        // batch k scores while the device parses batch k + 1 (second stream) and the reader thread fills the idle buffer with k + 2
+        std::vector<uint64_t> sizes(kept.size());
+        for (size_t k = 0; k < kept.size(); k++) {
+            struct stat st;
+            if (stat(kept[k].c_str(), &st) != 0) Die("Could not open file  %s", kept[k].c_str());
+            sizes[k] = (uint64_t)st.st_size;
+        }
+        const size_t n_batches = (kept.size() + (size_t)B - 1) / (size_t)B;
+        size_t cap = 1;
+        for (size_t b = 0; b < n_batches; b++) {
+            size_t sum = 0;
+            for (size_t k = b * B; k < std::min(kept.size(), (b + 1) * (size_t)B); k++) sum += sizes[k];
+            cap = std::max(cap, sum);
+        }
+        FileBatch fb[2];
+        for (FileBatch &f : fb) {
+            f.buf = (unsigned char *)malloc(cap);
+            if (!f.buf) Die("out of memory for the ICM files of a batch");
+            Check(gmg_host_register(f.buf, cap), "gmg_host_register");
+        }
+        void *load_stream = nullptr;
+        Check(gmg_stream_create(&load_stream), "gmg_stream_create");
+        auto first_of = [&](size_t b) { return b * (size_t)B; };
+        auto count_of = [&](size_t b) { return (int)std::min<size_t>((size_t)B, kept.size() - first_of(b)); };
+        auto fill = [&](size_t b) { fb[b & 1].Fill(kept, sizes, first_of(b), count_of(b)); };
+        auto queue_load = [&](size_t b) -> gmg_model_set * {        // (the reader of batch b has been joined)
+            FileBatch &f = fb[b & 1];
+            const int nb = count_of(b);
+            if (!f.error.empty()) Die("%s", f.error.c_str());
+            for (int k = 0; k < nb; k++) {              // (the header checks of the load itself, here with the path)
+                uint64_t blob = 0;
+                if (gmg_icm_bytes_info(f.ptr[k], f.size[k], nullptr, nullptr, nullptr, nullptr, &blob) != GMG_OK)
+                    Die("%s: %s", kept[first_of(b) + k].c_str(), gmg_last_error());
+            }
+            gmg_model_set *set = nullptr;
+            Check(gmg_model_set_load(f.ptr.data(), f.size.data(), nb, &set, load_stream), "gmg_model_set_load");
+            return set;
+        };
+        auto finish = [&](gmg_model_set *set, size_t b) {
+            int bad = -1;
+            if (gmg_model_set_finish(set, &bad) != GMG_OK) {
+                if (bad < 0) Check(GMG_EHIP, "gmg_model_set_finish");
+                Die("%s: %s", kept[first_of(b) + bad].c_str(), gmg_last_error());
+            }
+        };
+        fill(0);
+        gmg_model_set *cur = queue_load(0), *next = nullptr;
+        finish(cur, 0);
+        std::thread reader;
+        if (n_batches > 1) reader = std::thread(fill, (size_t)1);
+        for (size_t b = 0; b < n_batches; b++) {
+            if (b + 1 < n_batches) {
+                reader.join();
+                next = queue_load(b + 1);
+                // the buffer of batch b is idle (its load finished before this iteration) and nothing below reads fb[b & 1]: until
+                // the next join it belongs to the reader, which fills it with batch b + 2 while batch b scores
+                if (b + 2 < n_batches) reader = std::thread(fill, b + 2);
+            }
+            std::vector<const gmg_model *> dev(count_of(b));
+            for (size_t k = 0; k < dev.size(); k++) dev[k] = gmg_model_set_model(cur, (int)k);
+            score_batch(dev, first_of(b));
+            if (b + 1 < n_batches) finish(next, b + 1);
+            gmg_model_set_free(cur);
+            cur = next;
+            next = nullptr;
+        }
+        Check(gmg_stream_destroy(load_stream), "gmg_stream_destroy");
+        for (FileBatch &f : fb) {
+            gmg_host_unregister(f.buf);
+            free(f.buf);
+        }
     }
     if (raw) {
         fputs("END_DATA_MATRIX\n", raw);
