@@ -601,6 +601,102 @@ def find_orfs(reads, min_gene_len=75, allow_truncated=False, start_codons=("atg"
     return orfs[:n_orfs.value], off
 
 
+class OrfResult:
+    """A gmg_find_orfs result that stays on the device (gmg_mg_result): what gmg_entropy_orfs reads.  fetch() -> (orfs, read_orf_off)"""
+
+    def __init__(self, reads, min_gene_len=75, allow_truncated=False, start_codons=("atg", "gtg", "ttg"),
+                 stop_codons=("taa", "tag", "tga"), circular=False):
+        prm = capi.MgParams(min_gene_len, int(allow_truncated), 2**31 - 1, len(start_codons), len(stop_codons), 0, 0.0)
+        for i, c in enumerate(start_codons):
+            prm.start_codon[i].value = c.encode()
+        for i, c in enumerate(stop_codons):
+            prm.stop_codon[i].value = c.encode()
+        prm.circular = int(bool(circular))
+        self.h = C.c_void_p()
+        self.n_reads = reads.n_reads
+        _ck(capi.lib().gmg_find_orfs(reads.h, C.byref(prm), C.byref(self.h), None))
+        n_orfs, n_starts = C.c_uint64(), C.c_uint64()
+        _ck(capi.lib().gmg_mg_result_info(self.h, C.byref(n_orfs), C.byref(n_starts)))
+        self.n_orfs = int(n_orfs.value)
+
+    def fetch(self):
+        orfs = np.zeros(max(self.n_orfs, 1), MG_ORF_DTYPE)
+        off = np.zeros(self.n_reads + 1, np.uint64)
+        _ck(capi.lib().gmg_mg_result_fetch(self.h, _ptr(orfs), None, _ptr(off)))
+        return orfs[:self.n_orfs], off
+
+    def close(self):
+        if self.h:
+            capi.lib().gmg_mg_result_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def xlate_table(code):
+    """gmg_xlate_table: Codon_Translation (gene.cc:1016-1080) of the 64 codons (index 16*b0 + 4*b1 + b2, a=0 c=1 g=2 t=3) -> bytes"""
+    buf = C.create_string_buffer(64)
+    _ck(capi.lib().gmg_xlate_table(int(code), buf))
+    return buf.raw
+
+
+def entropy_default_profiles():
+    """gmg_entropy_default_profiles -> (pos[20], neg[20])"""
+    pos, neg = np.zeros(20), np.zeros(20)
+    _ck(capi.lib().gmg_entropy_default_profiles(_ptr(pos), _ptr(neg)))
+    return pos, neg
+
+
+def entropy_from_counts(counts, pos, neg):
+    """gmg_entropy_from_counts: the host finish of count vectors [n, 20] (or [20]) -> float64 [n, 3] (or [3]): pos_dist, neg_dist, ratio"""
+    counts = np.ascontiguousarray(counts, np.int32)
+    pos, neg = np.ascontiguousarray(pos, np.float64), np.ascontiguousarray(neg, np.float64)
+    rows = counts.reshape(-1, 20)
+    out = np.zeros((len(rows), 3))
+    a, b, c = C.c_double(), C.c_double(), C.c_double()
+    for k, row in enumerate(rows):
+        _ck(capi.lib().gmg_entropy_from_counts(_ptr(row), _ptr(pos), _ptr(neg), C.byref(a), C.byref(b), C.byref(c)))
+        out[k] = a.value, b.value, c.value
+    return out.reshape(counts.shape[:-1] + (3,))
+
+
+def _entropy_call(n, want_counts, want_dist, call):
+    """runs call(d_counts, d_dist) with device buffers for n rows -> (counts int32 [n, 20] or None, dist float64 [n, 3] or None)"""
+    cbuf = _DeviceBuffer(max(n, 1) * 80) if want_counts else None
+    dbuf = _DeviceBuffer(max(n, 1) * 24) if want_dist else None
+    try:
+        _ck(call(cbuf.ptr if cbuf else None, dbuf.ptr if dbuf else None))
+        _ck(capi.lib().gmg_synchronize(None))
+        counts = cbuf.to_host(np.int32, n * 20).reshape(n, 20) if cbuf else None
+        dist = dbuf.to_host(np.float64, n * 3).reshape(n, 3) if dbuf else None
+    finally:
+        for b in (cbuf, dbuf):
+            if b:
+                b.free()
+    return counts, dist
+
+
+def entropy_regions(reads, regions, aa, pos, neg, want_counts=True, want_dist=True):
+    """gmg_entropy_regions: regions = [(read, first, len, strand)] -> (counts [n, 20] or None, dist [n, 3] or None)"""
+    arr = (capi.GeneRegion * max(len(regions), 1))(*[capi.GeneRegion(int(r), int(f), int(ln), int(s)) for r, f, ln, s in regions])
+    aa = bytes(aa)
+    pos, neg = np.ascontiguousarray(pos, np.float64), np.ascontiguousarray(neg, np.float64)
+    return _entropy_call(len(regions), want_counts, want_dist, lambda c, d: capi.lib().gmg_entropy_regions(
+        reads.h, arr, len(regions), aa, _ptr(pos), _ptr(neg), c, d, None))
+
+
+def entropy_orfs(reads, orf_result, aa, pos, neg, want_counts=True, want_dist=True):
+    """gmg_entropy_orfs on an OrfResult -> (counts [n_orfs, 20] or None, dist [n_orfs, 3] or None)"""
+    aa = bytes(aa)
+    pos, neg = np.ascontiguousarray(pos, np.float64), np.ascontiguousarray(neg, np.float64)
+    return _entropy_call(orf_result.n_orfs, want_counts, want_dist, lambda c, d: capi.lib().gmg_entropy_orfs(
+        reads.h, orf_result.h, aa, _ptr(pos), _ptr(neg), c, d, None))
+
+
 START_ERRORS_DTYPE = np.dtype([("pos", "<i4", (2,)), ("type", "i1", (2,)), ("n", "i1"), ("reserved", "i1")])
 MG_ACCEPTED_ONLY, MG_ALLOW_INDELS, MG_ALLOW_SUBS = 1, 2, 4
 

@@ -16,6 +16,10 @@ class Segment(C.Structure):
     _fields_ = [("read", C.c_uint32), ("lo", C.c_uint32), ("len", C.c_uint32), ("orient", C.c_uint32)]
 
 
+class GeneRegion(C.Structure):
+    _fields_ = [("read", C.c_uint32), ("first", C.c_int32), ("len", C.c_int32), ("strand", C.c_int32)]
+
+
 class MgGroup(C.Structure):
     _fields_ = [("gene", C.c_void_p), ("read_begin", C.c_uint64), ("read_end", C.c_uint64)]
 
@@ -125,6 +129,11 @@ PROTOTYPES = {
     "gmg_classes_plan": (i32, [vp, vp, vp, u64, vp, vp, vp, vp, C.POINTER(u64)]),
     "gmg_stop_codons_by_code": (i32, [i32, vp, C.POINTER(i32)]),
     "gmg_ignore_score_len": (i32, [C.c_double, vp, i32, C.POINTER(C.c_int32)]),
+    "gmg_xlate_table": (i32, [i32, vp]),
+    "gmg_entropy_regions": (i32, [vp, vp, u64, vp, vp, vp, vp, vp, vp]),
+    "gmg_entropy_orfs": (i32, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "gmg_entropy_from_counts": (i32, [vp, vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gmg_entropy_default_profiles": (i32, [vp, vp]),
     "gmg_trainer_create": (i32, [vp, i32, i32, i32, C.POINTER(vp)]),
     "gmg_trainer_level_counts": (i32, [vp, i32, vp, vp]),
     "gmg_trainer_free": (i32, [vp]),

@@ -283,6 +283,45 @@ extern "C" int gmg_stop_codons_by_code(int code, char stop_codon[8][4], int *n_s
     return GMG_OK;
 }
 
+// Codon_Translation (src/Common/gene.cc:1016-1080) for the 64 codons of a GenBank translation table: aa[16*b0 + 4*b1 + b2] in the
+// library's base code a=0 c=1 g=2 t=3.  The tables are NCBI's genetic codes: the standard code in NCBI's own t, c, a, g order and,
+// per table, the codons that differ from it.
+// (*) Three tables follow what Codon_Translation RETURNS where that is not NCBI's code, since its output is what long-orfs filters
+// by (tests/golden/codon_translation.txt holds the reference's answers): table 13 has agc = G and agg = R (NCBI: S and G), table 21
+// keeps aaa = K (NCBI: N), table 22 has taa = L and tag = * (NCBI: the other way round).
+extern "C" int gmg_xlate_table(int code, char aa[64])
+{
+    if (!aa) return gmg_set_error(GMG_EINVAL, "gmg_xlate_table: NULL argument");
+    static const char standard[] = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG";
+    const char *diff = NULL;                            // "codon=letter" entries
+    switch (code) {
+    case 0: case 1: case 11: diff = ""; break;
+    case 2: diff = "aga=* agg=* ata=M tga=W"; break;                    // vertebrate mitochondrial
+    case 3: diff = "ata=M ctt=T ctc=T cta=T ctg=T tga=W"; break;        // yeast mitochondrial
+    case 4: diff = "tga=W"; break;                                      // mold, protozoan, coelenterate mitochondrial; mycoplasma
+    case 5: diff = "aga=S agg=S ata=M tga=W"; break;                    // invertebrate mitochondrial
+    case 6: diff = "taa=Q tag=Q"; break;                                // ciliate, dasycladacean, hexamita nuclear
+    case 9: diff = "aaa=N aga=S agg=S tga=W"; break;                    // echinoderm, flatworm mitochondrial
+    case 10: diff = "tga=C"; break;                                     // euplotid nuclear
+    case 12: diff = "ctg=S"; break;                                     // alternative yeast nuclear
+    case 13: diff = "aga=G agc=G agg=R ata=M tga=W"; break;             // ascidian mitochondrial (*)
+    case 14: diff = "aaa=N aga=S agg=S taa=Y tga=W"; break;             // alternative flatworm mitochondrial
+    case 15: diff = "tag=Q"; break;                                     // blepharisma nuclear
+    case 16: diff = "tag=L"; break;                                     // chlorophycean mitochondrial
+    case 21: diff = "tga=W ata=M aga=S agg=S"; break;                   // trematode mitochondrial (*)
+    case 22: diff = "tca=* taa=L tag=*"; break;                         // scenedesmus obliquus mitochondrial (*)
+    case 23: diff = "tta=*"; break;                                     // thraustochytrium mitochondrial
+    default:
+        return gmg_set_error(GMG_EINVAL, "ERROR:  Bad translation table = %d", code);
+    }
+    static const int ncbi_of_code[4] = {2, 1, 3, 0};                    // a, c, g, t in NCBI's t, c, a, g order
+    for (int i = 0; i < 64; i++)
+        aa[i] = standard[16 * ncbi_of_code[i >> 4] + 4 * ncbi_of_code[(i >> 2) & 3] + ncbi_of_code[i & 3]];
+    for (const char *p = diff; *p; p += p[5] ? 6 : 5)
+        aa[16 * gmg_base_code(p[0]) + 4 * gmg_base_code(p[1]) + gmg_base_code(p[2])] = p[4];
+    return GMG_OK;
+}
+
 // Set_Ignore_Score_Len (src/Glimmer/glimmer_base.cc:2597-2633): the longest ORF expected once at random in a million bases
 extern "C" int gmg_ignore_score_len(double gc_frac, const char (*stop_codon)[4], int n_stop_codons, int32_t *out)
 {

@@ -561,6 +561,41 @@ int gmg_classes_plan(const gmg_classes *c, const char *const *hdr, const uint32_
 int gmg_stop_codons_by_code(int code, char stop_codon[8][4], int *n_stop_codons);
 /* Set_Ignore_Score_Len (src/Glimmer/glimmer_base.cc:2597-2633) */
 int gmg_ignore_score_len(double gc_frac, const char (*stop_codon)[4], int n_stop_codons, int32_t *out);
+/* Codon_Translation (src/Common/gene.cc:1016-1080) as a table: aa[16*b0 + 4*b1 + b2] (base code a=0 c=1 g=2 t=3) = the amino-acid
+ * letter of the codon, '*' for a stop, under GenBank translation table `code` -- 0, 1 and 11 (one table), 2, 3, 4, 5, 6, 9, 10, 12,
+ * 13, 14, 15, 16, 21, 22, 23; GMG_EINVAL for any other. */
+int gmg_xlate_table(int code, char aa[64]);
+
+/* ---- the entropy distance ratio of an ORF (long-orfs -t, glimmer3 -E) ------------------------------------------------------
+ * Entropy_Distance_Ratio (src/Glimmer/long-orfs.cc:301-351, the same body in src/Glimmer/glimmer3.cc:423-473): the codons of a
+ * region are translated (Codon_Translation, src/Common/gene.cc:1016-1080), the 20 amino-acid counts become an entropy profile
+ * (Counts_To_Entropy_Profile, gene.cc:1095-1135) and the ratio is its Euclidean distance to the profile of genes over that to the
+ * profile of non-genes.
+ * A region is `len` bases of read `read` from the 0-based index `first`: read upwards (strand > 0, Forward_Strand_Transfer,
+ * gene.cc:1237-1260) or downwards and complemented (strand < 0, Reverse_Strand_Transfer, gene.cc:1533-1556), both modulo the
+ * read's length.  A trailing partial codon, '*' and every letter outside A C D E F G H I K L M N P Q R S T V W Y count nowhere.
+ * `aa` is a gmg_xlate_table; counts and profiles are in the order of those 20 letters.
+ * The COUNTS are the exact part: a file or a keep / drop decision should take d_counts through gmg_entropy_from_counts, which is
+ * the reference's arithmetic on the host bit for bit.  d_dist is finished on the device in the same order of operations and differs
+ * only through the device's log and d * d in place of pow (d, 2): below 1e-13 on both distances, NaN where the host gives NaN (a
+ * region of one amino acid), ratio = the IEEE quotient of the two distances (1.0 for 0 / 0, 1e3 for x / 0). */
+typedef struct gmg_gene_region { uint32_t read; int32_t first, len, strand; } gmg_gene_region;
+/* regions: HOST array.  d_counts [n][20] int32 and d_dist [n][3] double {pos_dist, neg_dist, ratio}: DEVICE, either may be NULL.
+ * first in [0, read length), 0 <= len <= read length, strand != 0: GMG_ERANGE otherwise; an aa entry that is neither 'A'..'Z' nor
+ * '*': GMG_EINVAL.  Stream-ordered and asynchronous. */
+int gmg_entropy_regions(const gmg_reads *reads, const gmg_gene_region *regions, uint64_t n, const char aa[64],
+                        const double pos[20], const double neg[20], int32_t *d_counts, double *d_dist, void *stream);
+/* the same for every ORF of a gmg_find_orfs / gmg_mg_score_reads result, which stays on the device: ORF k's region by
+ * Entropy_Filter's rule (long-orfs.cc:370-377) from its stop_position, gene_len and frame -- 1-based start stop_position - gene_len
+ * (forward) or stop_position + gene_len + 2 (reverse), brought onto the sequence as On_Seq_1 does (long-orfs.cc:1051-1065), len =
+ * gene_len -- modulo the read's length.  Rows in the result's ORF order. */
+int gmg_entropy_orfs(const gmg_reads *reads, const gmg_mg_result *orfs, const char aa[64], const double pos[20],
+                     const double neg[20], int32_t *d_counts, double *d_dist, void *stream);
+/* host, libm, the reference's order of operations: the bit-identical finish of one count vector (any output may be NULL) */
+int gmg_entropy_from_counts(const int32_t counts[20], const double pos[20], const double neg[20],
+                            double *pos_dist, double *neg_dist, double *ratio);
+/* DEFAULT_POS_ENTROPY_PROF / DEFAULT_NEG_ENTROPY_PROF (src/Common/gene.hh:47-52) */
+int gmg_entropy_default_profiles(double pos[20], double neg[20]);
 
 /* ---- build-icm: training counts on the device ---------------------------------------
  * Replaces the counting of ICM_Training_t: Count_Char_Pairs for the roots (src/ICM/icm.cc:1841-1870, called from
