@@ -170,6 +170,11 @@ PROTOTYPES = {
     "gmg_fixed_icm_free": (i32, [vp]),
 }
 
+# debug exports: not declared in include/*.h
+DEBUG_PROTOTYPES = {
+    "gmg_debug_cache_stats": (i32, [vp]),   # out[4]: busy blocks, busy bytes, idle blocks, idle bytes of the device block cache
+}
+
 
 def lib():
     global _lib
@@ -179,7 +184,7 @@ def lib():
                                "there is no fallback path" % LIB)
         # GMG_LIB_PATH: a variant build of the same sources (kernel experiments, tools/build_variants.sh); never a fallback
         _lib = C.CDLL(os.environ.get("GMG_LIB_PATH") or LIB)
-        for name, (res, args) in PROTOTYPES.items():
+        for name, (res, args) in list(PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
             fn = getattr(_lib, name)      # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

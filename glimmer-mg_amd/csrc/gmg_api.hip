@@ -518,6 +518,24 @@ static int finish_reads(gmg_reads *r, const uint64_t *h_off /* may be NULL */)
     return GMG_OK;
 }
 
+// The same for a batch built on the device (gmg_reads_select, gmg_fasta_ingest): the tile table comes from the cache, held by the
+// call's scratch until the reads take it, and is queued on s -- no wait; the lengths' statistics come from three counters a kernel of
+// the caller's has left: {shortest read, longest read, reads over 512 bases}.
+int gmg_reads_tile_table(gmg_reads *r, GmgScratch &sc, hipStream_t s)
+{
+    r->n_tiles = (r->total_bases + GMG_TILE - 1) / GMG_TILE;
+    GMG_HIP(sc.alloc(&r->d_tile_read, (r->n_tiles + 1) * sizeof(uint32_t)));
+    return gmg_launch_tile_read(r->d_off, r->n_reads, r->n_tiles, r->d_tile_read, s);
+}
+
+void gmg_reads_set_lengths(gmg_reads *r, const unsigned long long stats[3])
+{
+    r->min_len = r->n_reads ? stats[0] : 0;
+    r->max_len = stats[1];
+    r->n_over_512 = stats[2];
+    r->uniform_len = (r->n_reads && stats[0] == stats[1] && stats[0] > 0 && stats[0] < (1u << 30)) ? (int)stats[0] : 0;
+}
+
 // Packed reads always live in a library-owned buffer with GMG_GUARD_WORDS zero words on both
 // sides, so that window loads around the first and last bases of the job stay inside it.
 static int alloc_packed(gmg_reads *r, const uint32_t *src, hipMemcpyKind kind)
@@ -692,73 +710,53 @@ extern "C" int gmg_reads_select(const gmg_reads *reads, const uint64_t *idx, uin
 {
     { int rc_enter = gmg_enter("gmg_reads_select"); if (rc_enter) return rc_enter; }
     if (!reads || (!idx && n) || !out || n >= 0x7ffffffeull) return gmg_set_error(GMG_EINVAL, "gmg_reads_select: bad argument");
-    gmg_reads *r = new (std::nothrow) gmg_reads();
-    if (!r) return gmg_set_error(GMG_ENOMEM, "gmg_reads_select: out of host memory");
-    memset(r, 0, sizeof *r);
-    r->n_reads = n;
-    r->owns_off = 1;
+    hipStream_t s = 0;
+    GmgScratch sc(GmgScratch::STREAM, s);               // (kernels already queued may still use the blocks that go back to the cache)
     uint64_t *d_idx = nullptr, *d_len = nullptr, *d_off = nullptr;
     unsigned long long *d_stats = nullptr;
-    void *d_tmp = nullptr;
-    auto fail = [&](int rc) {
-        (void)hipStreamSynchronize(0);                  // (kernels already queued may still use the blocks that go back to the cache)
-        if (d_idx) gmg_pool_release(d_idx);
-        if (d_len) gmg_pool_release(d_len);
-        if (d_stats) gmg_pool_release(d_stats);
-        if (d_tmp) gmg_pool_release(d_tmp);
-        gmg_reads_free(r);
-        return rc;
-    };
-#define SEL_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(gmg_set_error(e_ == hipErrorOutOfMemory ? GMG_ENOMEM : GMG_EHIP, "gmg_reads_select: %s", hipGetErrorString(e_))); } while (0)
-    SEL_TRY(gmg_pool_alloc((void **)&d_idx, (n ? n : 1) * 8));
-    SEL_TRY(gmg_pool_alloc((void **)&d_len, (n + 1) * 8));
-    SEL_TRY(gmg_pool_alloc((void **)&d_off, (n + 1) * 8));
-    r->d_off = d_off;
-    SEL_TRY(gmg_pool_alloc((void **)&d_stats, 8 * sizeof(unsigned long long)));
+    GMG_HIP(sc.alloc(&d_idx, (n ? n : 1) * 8));
+    GMG_HIP(sc.alloc(&d_len, (n + 1) * 8));
+    GMG_HIP(sc.alloc(&d_off, (n + 1) * 8));
+    GMG_HIP(sc.alloc(&d_stats, 8 * sizeof(unsigned long long)));
     const unsigned long long stats0[6] = {~0ull, 0, 0, 0, ~0ull, 0};
     unsigned long long stats[6];
-    hipStream_t s = 0;
-    SEL_TRY(hipMemcpyAsync(d_stats, stats0, sizeof stats0, hipMemcpyHostToDevice, s));
-    if (n) SEL_TRY(hipMemcpyAsync(d_idx, idx, n * 8, hipMemcpyHostToDevice, s));
+    GMG_HIP(hipMemcpyAsync(d_stats, stats0, sizeof stats0, hipMemcpyHostToDevice, s));
+    if (n) GMG_HIP(hipMemcpyAsync(d_idx, idx, n * 8, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_sel_len, dim3((unsigned)((n + 256) / 256 < 512 ? (n + 256) / 256 : 512)), dim3(256), 0, s, reads->d_off, d_idx, n, reads->n_reads, d_len, d_stats);
-    SEL_TRY((gmg_scan_excl<uint64_t, uint64_t>(d_len, d_off, n + 1, s)));
-    SEL_TRY(hipMemcpyAsync(&stats[5], d_off + n, 8, hipMemcpyDeviceToHost, s));
-    SEL_TRY(hipMemcpyAsync(stats, d_stats, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    SEL_TRY(hipStreamSynchronize(s));
+    GMG_HIP((gmg_scan_excl<uint64_t, uint64_t>(d_len, d_off, n + 1, s)));
+    GMG_HIP(hipMemcpyAsync(&stats[5], d_off + n, 8, hipMemcpyDeviceToHost, s));
+    GMG_HIP(hipMemcpyAsync(stats, d_stats, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    GMG_HIP(hipStreamSynchronize(s));
     if (stats[4] != ~0ull)
-        return fail(gmg_set_error(GMG_ERANGE, "gmg_reads_select: entry %llu names a read beyond the batch's %llu", stats[4], (unsigned long long)reads->n_reads));
-    r->total_bases = stats[5];
+        return gmg_set_error(GMG_ERANGE, "gmg_reads_select: entry %llu names a read beyond the batch's %llu", stats[4], (unsigned long long)reads->n_reads);
     // the packed words (guards zeroed; the gather writes every data word), the tile table, the gather
-    const uint64_t data_words = (r->total_bases + 15) / 16;
-    r->n_words = data_words + GMG_GUARD_WORDS;
+    const uint64_t total = stats[5], data_words = (total + 15) / 16;
     uint32_t *alloc = nullptr;
-    SEL_TRY(gmg_pool_alloc((void **)&alloc, (data_words + 2 * GMG_GUARD_WORDS) * 4));
-    r->d_packed_alloc = alloc;
-    r->d_packed = alloc + GMG_GUARD_WORDS;
-    SEL_TRY(hipMemsetAsync(alloc, 0, GMG_GUARD_WORDS * 4, s));
-    SEL_TRY(hipMemsetAsync(alloc + GMG_GUARD_WORDS + data_words, 0, GMG_GUARD_WORDS * 4, s));
-    r->n_tiles = (r->total_bases + GMG_TILE - 1) / GMG_TILE;
-    SEL_TRY(gmg_pool_alloc((void **)&r->d_tile_read, (r->n_tiles + 1) * sizeof(uint32_t)));
-    {
-        const int rc = gmg_launch_tile_read(r->d_off, r->n_reads, r->n_tiles, r->d_tile_read, s);
-        if (rc) return fail(rc);
-    }
+    GMG_HIP(sc.alloc(&alloc, (data_words + 2 * GMG_GUARD_WORDS) * 4));
+    GMG_HIP(hipMemsetAsync(alloc, 0, GMG_GUARD_WORDS * 4, s));
+    GMG_HIP(hipMemsetAsync(alloc + GMG_GUARD_WORDS + data_words, 0, GMG_GUARD_WORDS * 4, s));
+    gmg_reads tmp;                                      // (the batch goes to the heap once nothing can fail any more)
+    memset(&tmp, 0, sizeof tmp);
+    tmp.n_reads = n;
+    tmp.total_bases = total;
+    tmp.d_off = d_off;
+    tmp.owns_off = 1;
+    tmp.n_words = data_words + GMG_GUARD_WORDS;
+    tmp.d_packed_alloc = alloc;
+    tmp.d_packed = alloc + GMG_GUARD_WORDS;
+    { const int rc = gmg_reads_tile_table(&tmp, sc, s); if (rc) return rc; }
     if (data_words) {
-        const uint64_t blocks = (r->n_tiles + 3) / 4;      // one wave per tile
+        const uint64_t blocks = (tmp.n_tiles + 3) / 4;     // one wave per tile
         hipLaunchKernelGGL(k_reads_select, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, reads->d_packed, reads->d_off, d_idx,
-                           d_off, r->d_tile_read, n, r->total_bases, alloc + GMG_GUARD_WORDS);
-        SEL_TRY(hipGetLastError());
+                           d_off, tmp.d_tile_read, n, total, alloc + GMG_GUARD_WORDS);
+        GMG_HIP(hipGetLastError());
     }
-    SEL_TRY(hipStreamSynchronize(s));
-#undef SEL_TRY
-    gmg_pool_release(d_idx);
-    gmg_pool_release(d_len);
-    gmg_pool_release(d_stats);
-    if (d_tmp) gmg_pool_release(d_tmp);
-    r->min_len = n ? stats[0] : 0;
-    r->max_len = stats[1];
-    r->n_over_512 = stats[2];
-    r->uniform_len = (n && stats[0] == stats[1] && stats[0] > 0 && stats[0] < (1u << 30)) ? (int)stats[0] : 0;
+    GMG_HIP(hipStreamSynchronize(s));
+    gmg_reads_set_lengths(&tmp, stats);
+    gmg_reads *r = new (std::nothrow) gmg_reads(tmp);
+    if (!r) return gmg_set_error(GMG_ENOMEM, "gmg_reads_select: out of host memory");
+    sc.detach(d_off); sc.detach(alloc); sc.detach(tmp.d_tile_read);
+    sc.wait = GmgScratch::NONE;                         // (waited for just now)
     *out = r;
     return GMG_OK;
 }
@@ -1175,6 +1173,12 @@ struct PoolBlock { void *p; size_t bytes; bool busy; hipEvent_t pending; bool wa
 std::mutex g_pool_mutex;
 std::vector<PoolBlock> g_pool;
 
+// (under the mutex) blocks released "after the stream reaches here" (gmg_pool_release_after) whose event has passed are idle
+void pool_retire()
+{
+    for (auto &b : g_pool)
+        if (b.busy && b.waiting && hipEventQuery(b.pending) == hipSuccess) { b.busy = false; b.waiting = false; }
+}
 }  // namespace
 
 hipError_t gmg_pool_alloc(void **out, size_t bytes)
@@ -1182,8 +1186,7 @@ hipError_t gmg_pool_alloc(void **out, size_t bytes)
     if (bytes == 0) bytes = 1;
     std::lock_guard<std::mutex> lock(g_pool_mutex);
     int best = -1;
-    for (auto &b : g_pool)                              // blocks released "after the stream reaches here" (gmg_pool_release_after)
-        if (b.busy && b.waiting && hipEventQuery(b.pending) == hipSuccess) { b.busy = false; b.waiting = false; }
+    pool_retire();
     for (size_t i = 0; i < g_pool.size(); i++)
         if (!g_pool[i].busy && g_pool[i].bytes >= bytes && g_pool[i].bytes <= 2 * bytes + 4096 &&
             (best < 0 || g_pool[i].bytes < g_pool[best].bytes))
@@ -1230,14 +1233,27 @@ void gmg_pool_release(void *p)
 extern "C" int gmg_trim_cache(void)
 {
     std::lock_guard<std::mutex> lock(g_pool_mutex);
-    for (auto &b : g_pool)
-        if (b.busy && b.waiting && hipEventQuery(b.pending) == hipSuccess) { b.busy = false; b.waiting = false; }
+    pool_retire();
     for (size_t i = 0; i < g_pool.size();)
         if (!g_pool[i].busy) { if (g_pool[i].pending) (void)hipEventDestroy(g_pool[i].pending); (void)hipFree(g_pool[i].p); g_pool.erase(g_pool.begin() + i); } else i++;
     gmg_ingest_trim();                                  // (the page-locked header buffers gmg_fasta_ingest keeps)
     return GMG_OK;
 }
 
+// tests: the cache's blocks that are handed out and those that are not -- out[0 .. 3] = busy blocks, busy bytes, idle blocks, idle
+// bytes.  A call that has ended and whose handles are freed holds none (GmgScratch, gmg_internal.h).
+extern "C" int gmg_debug_cache_stats(uint64_t out[4])
+{
+    if (!out) return gmg_set_error(GMG_EINVAL, "gmg_debug_cache_stats: NULL argument");
+    std::lock_guard<std::mutex> lock(g_pool_mutex);
+    pool_retire();
+    out[0] = out[1] = out[2] = out[3] = 0;
+    for (const auto &b : g_pool) {
+        out[b.busy ? 0 : 2]++;
+        out[b.busy ? 1 : 3] += b.bytes;
+    }
+    return GMG_OK;
+}
 
 // Page-lock a host buffer the caller already owns (file bytes, result arrays): copies to and from it then run at
 // PCIe speed instead of through the runtime's staging buffers.

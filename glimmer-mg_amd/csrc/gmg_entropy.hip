@@ -195,17 +195,14 @@ extern "C" int gmg_entropy_regions(const gmg_reads *reads, const gmg_gene_region
             return gmg_set_error(GMG_ERANGE, "gmg_entropy_regions: region %llu (first %d, len %d, strand %d) does not fit read %u of length %llu",
                                  (unsigned long long)i, r.first, r.len, r.strand, r.read, (unsigned long long)L);
     }
+    GmgScratch sc(GmgScratch::AFTER, s);
     gmg_gene_region *d_regions = nullptr;
-    if (gmg_pool_alloc((void **)&d_regions, n * sizeof(gmg_gene_region)) != hipSuccess)
+    if (sc.alloc(&d_regions, n * sizeof(gmg_gene_region)) != hipSuccess)
         return gmg_set_error(GMG_ENOMEM, "gmg_entropy_regions: no device memory for %llu regions", (unsigned long long)n);
-    hipError_t e = hipMemcpyAsync(d_regions, regions, n * sizeof(gmg_gene_region), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_entropy<false>, dim3(en_grid(n)), dim3(EN_BLOCK), 0, s, a, reads->d_packed, reads->d_off, d_regions,
-                           (const gmg_mg_orf *)nullptr, n, d_counts, d_dist);
-        e = hipGetLastError();
-    }
-    gmg_pool_release_after(d_regions, s);
-    if (e != hipSuccess) return gmg_set_error(GMG_EHIP, "gmg_entropy_regions: %s", hipGetErrorString(e));
+    GMG_HIP(hipMemcpyAsync(d_regions, regions, n * sizeof(gmg_gene_region), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_entropy<false>, dim3(en_grid(n)), dim3(EN_BLOCK), 0, s, a, reads->d_packed, reads->d_off, d_regions,
+                       (const gmg_mg_orf *)nullptr, n, d_counts, d_dist);
+    GMG_HIP(hipGetLastError());
     return GMG_OK;
 }
 

@@ -976,25 +976,20 @@ int gmg_launch_gene6_groups(const gmg_model *const *models, const uint64_t *grou
     constexpr uint32_t SPAN = 2 * BLOCK;
 
     // the groups' first bases
+    GmgScratch sc(GmgScratch::STREAM, s);
     std::vector<uint64_t> base(n_groups + 1);
     {
         uint64_t *d_idx = nullptr, *d_val = nullptr;
-        GMG_HIP(gmg_pool_alloc((void **)&d_idx, (size_t)(n_groups + 1) * 8));
-        hipError_t e = gmg_pool_alloc((void **)&d_val, (size_t)(n_groups + 1) * 8);
-        if (e != hipSuccess) {                          // (a block handed out and not given back stays busy for good)
-            gmg_pool_release(d_idx);
-            return gmg_set_error(e == hipErrorOutOfMemory ? GMG_ENOMEM : GMG_EHIP, "gmg_launch_gene6_groups: %s", hipGetErrorString(e));
-        }
-        e = hipMemcpyAsync(d_idx, group_read, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_f6_gather_u64, dim3((n_groups + 256) / 256), dim3(256), 0, s, reads->d_off, d_idx, (uint32_t)(n_groups + 1), d_val);
-            e = hipMemcpyAsync(base.data(), d_val, (size_t)(n_groups + 1) * 8, hipMemcpyDeviceToHost, s);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        gmg_pool_release(d_idx);
-        gmg_pool_release(d_val);
-        if (e != hipSuccess) return gmg_set_error(GMG_EHIP, "gmg_launch_gene6_groups: %s", hipGetErrorString(e));
+        GMG_HIP(sc.alloc(&d_idx, (size_t)(n_groups + 1) * 8));
+        GMG_HIP(sc.alloc(&d_val, (size_t)(n_groups + 1) * 8));
+        GMG_HIP(hipMemcpyAsync(d_idx, group_read, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_f6_gather_u64, dim3((n_groups + 256) / 256), dim3(256), 0, s, reads->d_off, d_idx, (uint32_t)(n_groups + 1), d_val);
+        GMG_HIP(hipMemcpyAsync(base.data(), d_val, (size_t)(n_groups + 1) * 8, hipMemcpyDeviceToHost, s));
+        GMG_HIP(hipStreamSynchronize(s));
+        sc.release(d_idx);
+        sc.release(d_val);
     }
+    sc.wait = GmgScratch::AFTER;                        // nothing below waits: what is still out goes back behind the stream
 
     Frame6Args a;
     a.gene = models[0]->dev;
@@ -1054,23 +1049,15 @@ int gmg_launch_gene6_groups(const gmg_model *const *models, const uint64_t *grou
     F6Range *d_ranges = nullptr;
     GmgDevModel *d_gm = nullptr;
     uint64_t *d_gread = nullptr;
-    hipError_t e = gmg_pool_alloc((void **)&d_rounds, (rounds.size() + 1) * sizeof(F6Round));
-    if (e == hipSuccess) e = gmg_pool_alloc((void **)&d_ranges, (ranges.size() + 1) * sizeof(F6Range));
-    if (e == hipSuccess) e = gmg_pool_alloc((void **)&d_gm, gm.size() * sizeof(GmgDevModel));
-    if (e == hipSuccess) e = gmg_pool_alloc((void **)&d_gread, (size_t)(n_groups + 1) * 8);
-    if (e == hipSuccess && !rounds.empty()) e = hipMemcpyAsync(d_rounds, rounds.data(), rounds.size() * sizeof(F6Round), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && !ranges.empty()) e = hipMemcpyAsync(d_ranges, ranges.data(), ranges.size() * sizeof(F6Range), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_gm, gm.data(), gm.size() * sizeof(GmgDevModel), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_gread, group_read, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);               // (the host vectors go away with this call)
-    auto done = [&](int rc) {
-        gmg_pool_release_after(d_rounds, s);
-        gmg_pool_release_after(d_ranges, s);
-        gmg_pool_release_after(d_gm, s);
-        gmg_pool_release_after(d_gread, s);
-        return rc;
-    };
-    if (e != hipSuccess) return done(gmg_set_error(GMG_EHIP, "gmg_launch_gene6_groups: %s", hipGetErrorString(e)));
+    GMG_HIP(sc.alloc(&d_rounds, (rounds.size() + 1) * sizeof(F6Round)));
+    GMG_HIP(sc.alloc(&d_ranges, (ranges.size() + 1) * sizeof(F6Range)));
+    GMG_HIP(sc.alloc(&d_gm, gm.size() * sizeof(GmgDevModel)));
+    GMG_HIP(sc.alloc(&d_gread, (size_t)(n_groups + 1) * 8));
+    if (!rounds.empty()) GMG_HIP(hipMemcpyAsync(d_rounds, rounds.data(), rounds.size() * sizeof(F6Round), hipMemcpyHostToDevice, s));
+    if (!ranges.empty()) GMG_HIP(hipMemcpyAsync(d_ranges, ranges.data(), ranges.size() * sizeof(F6Range), hipMemcpyHostToDevice, s));
+    GMG_HIP(hipMemcpyAsync(d_gm, gm.data(), gm.size() * sizeof(GmgDevModel), hipMemcpyHostToDevice, s));
+    GMG_HIP(hipMemcpyAsync(d_gread, group_read, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, s));
+    GMG_HIP(hipStreamSynchronize(s));                               // (the host vectors go away with this call)
     a.rounds = d_rounds;
     a.n_rounds = (uint32_t)rounds.size();
     a.ranges = d_ranges;
@@ -1081,24 +1068,23 @@ int gmg_launch_gene6_groups(const gmg_model *const *models, const uint64_t *grou
 
     if (!rounds.empty()) {
         int dev = 0, n_cu = 256;
-        if ((e = hipGetDevice(&dev)) != hipSuccess || (e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess)
-            return done(gmg_set_error(GMG_EHIP, "gmg_launch_gene6_groups: %s", hipGetErrorString(e)));
+        GMG_HIP(hipGetDevice(&dev));
+        GMG_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
         unsigned nworkers = (unsigned)(n_cu / 3);
         if (nworkers < 1) nworkers = 1;
         if (nworkers > rounds.size()) nworkers = (unsigned)rounds.size();
         const unsigned grid = 3 * nworkers;
         const size_t lds = ((size_t)1 << (2 * DT)) * 8;
         if ((gstride & 1) == 0) {
-            e = hipFuncSetAttribute((const void *)k_frame6t<BLOCK, DT, KR, 0, true, true, false, false, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess) hipLaunchKernelGGL((k_frame6t<BLOCK, DT, KR, 0, true, true, false, false, true>), dim3(grid), dim3(BLOCK), lds, s, a);
+            GMG_HIP(hipFuncSetAttribute((const void *)k_frame6t<BLOCK, DT, KR, 0, true, true, false, false, true>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL((k_frame6t<BLOCK, DT, KR, 0, true, true, false, false, true>), dim3(grid), dim3(BLOCK), lds, s, a);
         } else {
-            e = hipFuncSetAttribute((const void *)k_frame6t<BLOCK, DT, KR, 0, false, true, false, false, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess) hipLaunchKernelGGL((k_frame6t<BLOCK, DT, KR, 0, false, true, false, false, true>), dim3(grid), dim3(BLOCK), lds, s, a);
+            GMG_HIP(hipFuncSetAttribute((const void *)k_frame6t<BLOCK, DT, KR, 0, false, true, false, false, true>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL((k_frame6t<BLOCK, DT, KR, 0, false, true, false, false, true>), dim3(grid), dim3(BLOCK), lds, s, a);
         }
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) return done(gmg_set_error(GMG_EHIP, "gmg_launch_gene6_groups: %s", hipGetErrorString(e)));
+        GMG_HIP(hipGetLastError());
     }
     // the partial-window heads of every read, group by group, and the ranges outside the rounds
     {
@@ -1108,12 +1094,11 @@ int gmg_launch_gene6_groups(const gmg_model *const *models, const uint64_t *grou
         a.p_blocks = grid;
         // (eight blocks per range: with one ICM per read -- up to 2^27 groups -- that would pass the grid limit only at launch time)
         if ((uint64_t)grid + 8ull * ranges.size() > 0x7fffffffull)
-            return done(gmg_set_error(GMG_ETOOBIG, "gmg_launch_gene6_groups: %llu group edges in one batch: split the batch", (unsigned long long)ranges.size()));
+            return gmg_set_error(GMG_ETOOBIG, "gmg_launch_gene6_groups: %llu group edges in one batch: split the batch", (unsigned long long)ranges.size());
         hipLaunchKernelGGL((k_frame6p<7, 4, true, true>), dim3(grid + 8 * (unsigned)ranges.size()), dim3(256), lds_p, s, a);
-        e = hipGetLastError();
-        if (e != hipSuccess) return done(gmg_set_error(GMG_EHIP, "gmg_launch_gene6_groups: %s", hipGetErrorString(e)));
+        GMG_HIP(hipGetLastError());
     }
-    return done(GMG_OK);
+    return GMG_OK;
 }
 
 // Per-base values of the two strings scoreReadsGlim scores with a periodicity-1 ICM (the read, and its reverse

@@ -31,6 +31,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <chrono>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -512,18 +513,15 @@ extern "C" int gmg_fasta_ingest_on(const char *bytes, uint64_t n_bytes, gmg_read
     };
     if ((!bytes && n_bytes) || !out_reads || !out_index) return gmg_set_error(GMG_EINVAL, "gmg_fasta_ingest: NULL argument");
     if (n_bytes >= 0x7fffffffull) return gmg_set_error(GMG_EINVAL, "gmg_fasta_ingest: at most 2^31 - 2 bytes per call");
-    gmg_fasta *idx = new (std::nothrow) gmg_fasta();
+    struct IdxFree { void operator()(gmg_fasta *f) const { (void)gmg_fasta_free(f); } };     // (gives the page-locked header buffer back too)
+    std::unique_ptr<gmg_fasta, IdxFree> idx(new (std::nothrow) gmg_fasta());
     if (!idx) return gmg_set_error(GMG_ENOMEM, "gmg_fasta_ingest: out of host memory");
     idx->n_reads = idx->total_bases = idx->gc_count = 0;
-    // what goes to the gmg_reads: the packed words in their guarded buffer, the offsets (the guards are older than `dev`: on an early
-    // return they let go of the blocks AFTER dev's destructor has waited for the stream)
+    // every block of the call, the temporaries and what goes to the gmg_reads in the end (the packed words in their guarded buffer,
+    // the offsets, the tile table): back to the cache once the stream has drained, unless the reads have taken them
+    GmgScratch dev(GmgScratch::STREAM, st);
     uint32_t *d_alloc = nullptr;
     uint64_t *d_off = nullptr;
-    struct BufGuard { uint32_t *&p; ~BufGuard() { if (p) gmg_pool_release(p); } } alloc_guard = {d_alloc};   // until the reads own it
-    struct OffGuard { uint64_t *&p; ~OffGuard() { if (p) gmg_pool_release(p); } } off_guard = {d_off};       // until then it is ours
-    GmgScratch dev;                                     // temporaries: back to the cache once the stream has drained
-    dev.wait = GmgScratch::STREAM;
-    dev.st = st;
     uint8_t *d_bytes = nullptr, *d_func = nullptr, *d_bstate = nullptr;
     FaSumm *d_summ = nullptr;
     uint64_t *d_bexcl = nullptr, *d_tot = nullptr, n_blocks = 0;
@@ -531,15 +529,6 @@ extern "C" int gmg_fasta_ingest_on(const char *bytes, uint64_t n_bytes, gmg_read
     uint32_t *d_packed = nullptr;
     unsigned long long *d_gc = nullptr;
     void *d_tmp = nullptr;
-#define FA_TRY(call)                                                                                              \
-    do {                                                                                                          \
-        hipError_t e_ = (call);                                                                                   \
-        if (e_ != hipSuccess) {                                                                                   \
-            delete idx;                                                                                           \
-            return gmg_set_error(e_ == hipErrorOutOfMemory ? GMG_ENOMEM : GMG_EHIP, "gmg_fasta_ingest: %s: %s", #call, \
-                                 hipGetErrorString(e_));                                                          \
-        }                                                                                                         \
-    } while (0)
     const uint64_t n = n_bytes;
     uint64_t n_reads = 0, total = 0;
     // a chunked upload packs every piece as it arrives, into arrays sized by a bound: rec_cap records (16 file bytes per record; a file
@@ -550,17 +539,17 @@ extern "C" int gmg_fasta_ingest_on(const char *bytes, uint64_t n_bytes, gmg_read
     if (n) {
         const bool scans = gmg_opt(GMG_OPT_INGEST_SCANS) != 0;       // the first version: two scans over every byte
         n_blocks = (n + FA_BLK - 1) / FA_BLK;
-        FA_TRY(dev.alloc(&d_bytes, n + 16));
+        GMG_HIP(dev.alloc(&d_bytes, n + 16));
         if (scans) {
-            FA_TRY(dev.alloc(&d_func, n));
-            FA_TRY(dev.alloc(&d_count, (n + 1) * 8));
+            GMG_HIP(dev.alloc(&d_func, n));
+            GMG_HIP(dev.alloc(&d_count, (n + 1) * 8));
         } else {
-            FA_TRY(dev.alloc(&d_summ, n_blocks * sizeof(FaSumm)));
-            FA_TRY(dev.alloc(&d_bstate, n_blocks));
-            FA_TRY(dev.alloc(&d_bexcl, n_blocks * 8));
-            FA_TRY(dev.alloc(&d_tot, 16));
+            GMG_HIP(dev.alloc(&d_summ, n_blocks * sizeof(FaSumm)));
+            GMG_HIP(dev.alloc(&d_bstate, n_blocks));
+            GMG_HIP(dev.alloc(&d_bexcl, n_blocks * 8));
+            GMG_HIP(dev.alloc(&d_tot, 16));
         }
-        if (!scans) FA_TRY(hipMemsetAsync(d_tot, 0, 16, st));               // counts 0, state PRE in front of the first block
+        if (!scans) GMG_HIP(hipMemsetAsync(d_tot, 0, 16, st));               // counts 0, state PRE in front of the first block
         lap("alloc");
         // the upload in up to 16 pieces on a stream of its own, the first pass over a piece as soon as it has arrived (the pass is
         // hidden behind the next piece's copy; small inputs, the scans' form and a busy copy lane take one plain copy)
@@ -574,7 +563,7 @@ extern "C" int gmg_fasta_ingest_on(const char *bytes, uint64_t n_bytes, gmg_read
             // (queued on `st` behind the event: they run beside the first piece's copy)
             rec_cap = n / 16 + 1024;
             const uint64_t words_cap = (n + 15) / 16;
-            if (pe == hipSuccess) pe = gmg_pool_alloc((void **)&d_alloc, (words_cap + 2 * GMG_GUARD_WORDS + 1) * 4);
+            if (pe == hipSuccess) pe = dev.alloc(&d_alloc, (words_cap + 2 * GMG_GUARD_WORDS + 1) * 4);
             if (pe == hipSuccess) pe = dev.alloc(&d_off_big, (rec_cap + 1) * 8);
             if (pe == hipSuccess) pe = dev.alloc(&d_hb, rec_cap * 8);
             if (pe == hipSuccess) pe = dev.alloc(&d_he, rec_cap * 8);
@@ -604,19 +593,19 @@ extern "C" int gmg_fasta_ingest_on(const char *bytes, uint64_t n_bytes, gmg_read
             }
             if (pe != hipSuccess) (void)hipStreamSynchronize(cl.copy);
             cl.mu.unlock();
-            FA_TRY(pe);
+            GMG_HIP(pe);
         } else
-            FA_TRY(hipMemcpyAsync(d_bytes, bytes, n, hipMemcpyHostToDevice, st));
+            GMG_HIP(hipMemcpyAsync(d_bytes, bytes, n, hipMemcpyHostToDevice, st));
         lap("copy file to device");
         if (!scans) {
             if (!piecewise) {
                 hipLaunchKernelGGL(k_fa_summ, dim3((unsigned)(n_blocks < 256 * 64 ? n_blocks : 256 * 64)), dim3(256), 0, st, d_bytes, n, n_blocks, d_summ);
                 hipLaunchKernelGGL(k_fa_blocks, dim3(1), dim3(1024), 0, st, d_summ, (uint64_t)0, n_blocks, d_bstate, d_bexcl, d_tot);
             }
-            FA_TRY(hipGetLastError());
+            GMG_HIP(hipGetLastError());
             uint64_t tot[2] = {0, 0};
-            FA_TRY(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, st));
-            FA_TRY(hipStreamSynchronize(st));
+            GMG_HIP(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, st));
+            GMG_HIP(hipStreamSynchronize(st));
             lap("block summaries");
             n_reads = tot[0] >> FA_REC_SHIFT;
             total = tot[0] & ((1ull << FA_REC_SHIFT) - 1);
@@ -624,24 +613,24 @@ extern "C" int gmg_fasta_ingest_on(const char *bytes, uint64_t n_bytes, gmg_read
         // 1. the state behind every byte
         hipcub::TransformInputIterator<uint8_t, FaFuncOf, const uint8_t *> func_in(d_bytes, FaFuncOf());
         size_t tmp_bytes = 0, tmp2 = 0;
-        FA_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, tmp_bytes, func_in, d_func, FaCompose(), (int)n));
+        GMG_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, tmp_bytes, func_in, d_func, FaCompose(), (int)n));
         // 2. records and bases in front of every byte (entry n = the totals)
         hipcub::CountingInputIterator<uint64_t> pos(0);
         FaCountOf count_of = {d_bytes, d_func};
         hipcub::TransformInputIterator<uint64_t, FaCountOf, hipcub::CountingInputIterator<uint64_t>> count_in(pos, count_of);
-        FA_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, count_in, d_count, (int)n));
+        GMG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, count_in, d_count, (int)n));
         if (tmp2 > tmp_bytes) tmp_bytes = tmp2;
-        FA_TRY(dev.alloc(&d_tmp, tmp_bytes));
+        GMG_HIP(dev.alloc(&d_tmp, tmp_bytes));
         size_t tb = tmp_bytes;
-        FA_TRY(hipcub::DeviceScan::InclusiveScan(d_tmp, tb, func_in, d_func, FaCompose(), (int)n, st));
+        GMG_HIP(hipcub::DeviceScan::InclusiveScan(d_tmp, tb, func_in, d_func, FaCompose(), (int)n, st));
         tb = tmp_bytes;
-        FA_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, count_in, d_count, (int)n, st));
+        GMG_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, count_in, d_count, (int)n, st));
         uint64_t last_excl = 0;
         uint8_t last_func = 0, last_byte = 0, prev_func = 0;
-        FA_TRY(hipMemcpyAsync(&last_excl, d_count + (n - 1), 8, hipMemcpyDeviceToHost, st));
-        FA_TRY(hipMemcpyAsync(&last_func, d_func + (n - 1), 1, hipMemcpyDeviceToHost, st));
-        if (n > 1) FA_TRY(hipMemcpyAsync(&prev_func, d_func + (n - 2), 1, hipMemcpyDeviceToHost, st));
-        FA_TRY(hipStreamSynchronize(st));
+        GMG_HIP(hipMemcpyAsync(&last_excl, d_count + (n - 1), 8, hipMemcpyDeviceToHost, st));
+        GMG_HIP(hipMemcpyAsync(&last_func, d_func + (n - 1), 1, hipMemcpyDeviceToHost, st));
+        if (n > 1) GMG_HIP(hipMemcpyAsync(&prev_func, d_func + (n - 2), 1, hipMemcpyDeviceToHost, st));
+        GMG_HIP(hipStreamSynchronize(st));
         lap("two scans");
         last_byte = (uint8_t)bytes[n - 1];
         const unsigned st_last = n > 1 ? (prev_func & 3u) : (unsigned)ST_PRE;
@@ -651,40 +640,36 @@ extern "C" int gmg_fasta_ingest_on(const char *bytes, uint64_t n_bytes, gmg_read
         (void)last_func;
         }
     }
-    if (n_reads >= (1ull << 28)) { delete idx; return gmg_set_error(GMG_EINVAL, "gmg_fasta_ingest: too many records in one call"); }
+    if (n_reads >= (1ull << 28)) return gmg_set_error(GMG_EINVAL, "gmg_fasta_ingest: too many records in one call");
     // 3. pack, offsets, header extents, g/c count
     // (the packed words are written where they stay: the gmg_reads' buffer with its guard words on both sides)
     const uint64_t data_words = (total + 15) / 16;
     unsigned long long *d_stats = nullptr;
-    FA_TRY(dev.alloc(&d_stats, 32));
-    hipError_t e2 = hipSuccess;
+    GMG_HIP(dev.alloc(&d_stats, 32));
     if (spec && n_reads <= rec_cap) {
         // the pieces are packed already: the offsets move into an array of their size, the header extents that ran up to a piece's end are completed
-        FA_TRY(gmg_pool_alloc((void **)&d_off, (n_reads + 1) * 8));           // goes to the gmg_reads
-        if (n_reads) e2 = hipMemcpyAsync(d_off, d_off_big, n_reads * 8, hipMemcpyDeviceToDevice, st);
-        if (e2 == hipSuccess) e2 = hipMemcpyAsync(d_off + n_reads, &total, 8, hipMemcpyHostToDevice, st);
-        if (e2 == hipSuccess && n_reads) {
+        GMG_HIP(dev.alloc(&d_off, (n_reads + 1) * 8));                         // goes to the gmg_reads
+        if (n_reads) GMG_HIP(hipMemcpyAsync(d_off, d_off_big, n_reads * 8, hipMemcpyDeviceToDevice, st));
+        GMG_HIP(hipMemcpyAsync(d_off + n_reads, &total, 8, hipMemcpyHostToDevice, st));
+        if (n_reads) {
             const uint64_t blocks = (n_reads + 255) / 256;
             hipLaunchKernelGGL(k_fa_hdr_fix, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, d_bytes, n, d_hb, n_reads);
         }
-        if (e2 != hipSuccess) { delete idx; return gmg_set_error(GMG_EHIP, "gmg_fasta_ingest: %s", hipGetErrorString(e2)); }
     } else {
         if (spec) {                                     // more records than the bound: the arrays again, in their real size
-            gmg_pool_release(d_alloc);
-            d_alloc = nullptr;
+            dev.release(d_alloc);
             d_hb = d_he = nullptr;                      // (the bound-sized ones stay with `dev` until the call ends)
             spec = false;
         }
-        FA_TRY(gmg_pool_alloc((void **)&d_alloc, (data_words + 2 * GMG_GUARD_WORDS + 1) * 4));
+        GMG_HIP(dev.alloc(&d_alloc, (data_words + 2 * GMG_GUARD_WORDS + 1) * 4));
         d_packed = d_alloc + GMG_GUARD_WORDS;
-        FA_TRY(hipMemsetAsync(d_alloc, 0, (data_words + 2 * GMG_GUARD_WORDS + 1) * 4, st));
-        FA_TRY(gmg_pool_alloc((void **)&d_off, (n_reads + 1) * 8));           // goes to the gmg_reads
-        e2 = dev.alloc(&d_hb, n_reads * 8);
-        if (e2 == hipSuccess) e2 = dev.alloc(&d_he, n_reads * 8);
-        if (e2 == hipSuccess && !d_gc) e2 = dev.alloc(&d_gc, 8);
-        if (e2 == hipSuccess) e2 = hipMemsetAsync(d_gc, 0, 8, st);
-        if (e2 == hipSuccess) e2 = hipMemcpyAsync(d_off + n_reads, &total, 8, hipMemcpyHostToDevice, st);
-        if (e2 != hipSuccess) { delete idx; return gmg_set_error(GMG_ENOMEM, "gmg_fasta_ingest: %s", hipGetErrorString(e2)); }
+        GMG_HIP(hipMemsetAsync(d_alloc, 0, (data_words + 2 * GMG_GUARD_WORDS + 1) * 4, st));
+        GMG_HIP(dev.alloc(&d_off, (n_reads + 1) * 8));                         // goes to the gmg_reads
+        GMG_HIP(dev.alloc(&d_hb, n_reads * 8));
+        GMG_HIP(dev.alloc(&d_he, n_reads * 8));
+        if (!d_gc) GMG_HIP(dev.alloc(&d_gc, 8));
+        GMG_HIP(hipMemsetAsync(d_gc, 0, 8, st));
+        GMG_HIP(hipMemcpyAsync(d_off + n_reads, &total, 8, hipMemcpyHostToDevice, st));
         if (n_reads) {
             const uint64_t blocks = (n_reads + 255) / 256;
             hipLaunchKernelGGL(k_fa_fill, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, d_he, n_reads, n_bytes);
@@ -698,19 +683,20 @@ extern "C" int gmg_fasta_ingest_on(const char *bytes, uint64_t n_bytes, gmg_read
             hipLaunchKernelGGL(k_fa_pack, dim3((unsigned)(blocks < 256 * 32 ? blocks : 256 * 32)), dim3(256), 0, st, a);
         }
     }
-    e2 = hipGetLastError();
-    if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
+    GMG_HIP(hipGetLastError());
+    GMG_HIP(hipStreamSynchronize(st));
     lap("pack kernel");
     unsigned long long gc = 0;
     if (n_reads) {
         idx->hdr = (uint64_t *)pinned_cache().get(2 * n_reads * 8, idx->hdr_cap);
         if (!idx->hdr) { idx->hdr_cap = 0; idx->hdr_vec.resize(2 * n_reads); idx->hdr = idx->hdr_vec.data(); }
     }
-    if (e2 == hipSuccess && n_reads) e2 = hipMemcpyAsync(idx->hdr, d_hb, n_reads * 8, hipMemcpyDeviceToHost, st);
-    if (e2 == hipSuccess && n_reads) e2 = hipMemcpyAsync(idx->hdr + n_reads, d_he, n_reads * 8, hipMemcpyDeviceToHost, st);
-    if (e2 == hipSuccess) e2 = hipMemcpyAsync(&gc, d_gc, 8, hipMemcpyDeviceToHost, st);
-    if (e2 == hipSuccess) e2 = hipStreamSynchronize(st);
-    if (e2 != hipSuccess) { (void)gmg_fasta_free(idx); return gmg_set_error(GMG_EHIP, "gmg_fasta_ingest: %s", hipGetErrorString(e2)); }
+    if (n_reads) {
+        GMG_HIP(hipMemcpyAsync(idx->hdr, d_hb, n_reads * 8, hipMemcpyDeviceToHost, st));
+        GMG_HIP(hipMemcpyAsync(idx->hdr + n_reads, d_he, n_reads * 8, hipMemcpyDeviceToHost, st));
+    }
+    GMG_HIP(hipMemcpyAsync(&gc, d_gc, 8, hipMemcpyDeviceToHost, st));
+    GMG_HIP(hipStreamSynchronize(st));
     lap("headers to host");
     idx->n_reads = n_reads;                             // (begin at hdr[i], end at hdr[n_reads_as_copied + i]: kept for gmg_fasta_headers)
     const uint64_t n_copied = n_reads;
@@ -719,49 +705,36 @@ extern "C" int gmg_fasta_ingest_on(const char *bytes, uint64_t n_bytes, gmg_read
         n_reads--;                                      // fasta.cc:258-261: EOF while skipping the blanks -> return false
     // the gmg_reads around what is on the device already: the tile table, and the batch's length statistics from a reduction over
     // the offsets (gmg_reads_wrap_device copied the words once more and read 8 bytes per read back through pageable memory: 1.2 ms)
-    gmg_reads *reads = new (std::nothrow) gmg_reads();
-    if (!reads) { (void)gmg_fasta_free(idx); return gmg_set_error(GMG_ENOMEM, "gmg_fasta_ingest: out of host memory"); }
-    memset(reads, 0, sizeof *reads);
-    reads->n_reads = n_reads;
-    reads->total_bases = total;
-    reads->n_words = data_words + GMG_GUARD_WORDS;
-    reads->n_tiles = (total + GMG_TILE - 1) / GMG_TILE;
+    gmg_reads tmp;                                      // (the batch goes to the heap once nothing can fail any more)
+    memset(&tmp, 0, sizeof tmp);
+    tmp.n_reads = n_reads;
+    tmp.total_bases = total;
+    tmp.n_words = data_words + GMG_GUARD_WORDS;
+    tmp.d_packed_alloc = d_alloc;
+    tmp.d_packed = d_packed;
+    tmp.d_off = d_off;
+    tmp.owns_off = 1;
     unsigned long long stats[3] = {~0ull, 0, 0};
-    e2 = gmg_pool_alloc((void **)&reads->d_tile_read, (reads->n_tiles + 1) * sizeof(uint32_t));
-    if (e2 == hipSuccess) e2 = hipMemcpyAsync(d_stats, stats, 24, hipMemcpyHostToDevice, st);
-    int rc = 0;
-    if (e2 == hipSuccess) rc = gmg_launch_tile_read(d_off, n_reads, reads->n_tiles, reads->d_tile_read, st);
-    if (e2 == hipSuccess && !rc && n_reads) {
+    GMG_HIP(hipMemcpyAsync(d_stats, stats, 24, hipMemcpyHostToDevice, st));
+    { const int rc = gmg_reads_tile_table(&tmp, dev, st); if (rc) return rc; }
+    if (n_reads) {
         const uint64_t blocks = (n_reads + 255) / 256;
         hipLaunchKernelGGL(k_fa_stats, dim3((unsigned)(blocks < 128 ? blocks : 128)), dim3(256), 0, st, d_off, n_reads, d_stats);      // (few waves: three atomics each)
-        e2 = hipGetLastError();
+        GMG_HIP(hipGetLastError());
     }
-    if (e2 == hipSuccess && !rc) e2 = hipMemcpyAsync(stats, d_stats, 24, hipMemcpyDeviceToHost, st);
-    if (e2 == hipSuccess && !rc) e2 = hipStreamSynchronize(st);
-    if (e2 != hipSuccess || rc) {
-        if (reads->d_tile_read) gmg_pool_release(reads->d_tile_read);
-        delete reads;
-        (void)gmg_fasta_free(idx);
-        return rc ? rc : gmg_set_error(GMG_EHIP, "gmg_fasta_ingest: %s", hipGetErrorString(e2));
-    }
-    reads->d_packed_alloc = d_alloc;
-    reads->d_packed = d_packed;
-    reads->d_off = d_off;
-    reads->owns_off = 1;                                // buffer and offsets now belong to the reads
-    d_alloc = nullptr;
-    d_off = nullptr;
-    reads->min_len = n_reads ? stats[0] : 0;
-    reads->max_len = stats[1];
-    reads->n_over_512 = stats[2];
-    reads->uniform_len = (n_reads && stats[0] == stats[1] && stats[0] > 0 && stats[0] < (1u << 30)) ? (int)stats[0] : 0;
+    GMG_HIP(hipMemcpyAsync(stats, d_stats, 24, hipMemcpyDeviceToHost, st));
+    GMG_HIP(hipStreamSynchronize(st));
+    gmg_reads_set_lengths(&tmp, stats);
+    gmg_reads *reads = new (std::nothrow) gmg_reads(tmp);
+    if (!reads) return gmg_set_error(GMG_ENOMEM, "gmg_fasta_ingest: out of host memory");
+    dev.detach(d_alloc); dev.detach(d_off); dev.detach(tmp.d_tile_read);      // buffer, offsets and tile table now belong to the reads
     lap("reads object");
     idx->n_reads = n_reads;
     idx->hdr_stride = n_copied;
     idx->total_bases = total;
     idx->gc_count = gc;
     *out_reads = reads;
-    *out_index = idx;
-#undef FA_TRY
+    *out_index = idx.release();
     return GMG_OK;
 }
 

@@ -99,8 +99,8 @@ int gmg_enter(const char *who);
     do {                                                                                      \
         hipError_t e_ = (call);                                                               \
         if (e_ != hipSuccess)                                                                 \
-            return gmg_set_error(GMG_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
-                                 __FILE__, __LINE__);                                         \
+            return gmg_set_error(e_ == hipErrorOutOfMemory ? GMG_ENOMEM : GMG_EHIP, "%s failed: %s (%s:%d)", #call, \
+                                 hipGetErrorString(e_), __FILE__, __LINE__);                  \
     } while (0)
 
 // Tuning / test switches (gmg_set_option, include/gmg.h).  Set explicitly through the API, or once at gmg_init() from the
@@ -164,21 +164,25 @@ void gmg_pool_release(void *p);
 void gmg_pool_release_after(void *p, hipStream_t s);   // ... once the work queued on s so far is done
 
 // The blocks one call holds, by scope: whatever has not been released early or detached (handed to a result that outlives the
-// call) goes back to the cache when the holder ends -- behind a wait for the stream or the whole device where work that uses
-// the blocks may still be queued.
+// call) goes back to the cache when the holder ends.  Where work that uses the blocks may still be queued the holder waits for
+// the stream (STREAM) or the whole device (DEVICE) first, or -- an asynchronous entry point -- leaves the wait to the cache
+// (AFTER: the blocks are free once what is queued on the stream so far has run).  The mode may change during the call.
 struct __attribute__((visibility("hidden"))) GmgScratch {   // (hidden: no weak symbols of it among the library's exports)
-    enum Wait { NONE, STREAM, DEVICE };
+    enum Wait { NONE, STREAM, DEVICE, AFTER };
     Wait wait = NONE;
     hipStream_t st = nullptr;
     std::vector<void *> v;
     GmgScratch() {}
+    GmgScratch(Wait w, hipStream_t s) : wait(w), st(s) {}
     GmgScratch(const GmgScratch &) = delete;
     GmgScratch &operator=(const GmgScratch &) = delete;
     ~GmgScratch()
     {
         if (wait == STREAM) (void)hipStreamSynchronize(st);
         else if (wait == DEVICE) (void)hipDeviceSynchronize();
-        for (void *p : v) gmg_pool_release(p);
+        for (void *p : v)
+            if (wait == AFTER) gmg_pool_release_after(p, st);
+            else gmg_pool_release(p);
     }
     template <class T> hipError_t alloc(T **p, size_t bytes)
     {
@@ -199,6 +203,11 @@ struct __attribute__((visibility("hidden"))) GmgScratch {   // (hidden: no weak 
         p = nullptr;
     }
 };
+
+// the end of a batch of reads built on the device (gmg_api.hip): its tile table, queued on s; its lengths' statistics from the
+// counters {shortest, longest, reads over 512 bases}
+int gmg_reads_tile_table(gmg_reads *r, GmgScratch &sc, hipStream_t s);
+void gmg_reads_set_lengths(gmg_reads *r, const unsigned long long stats[3]);
 
 // kernel launchers (gmg_kernels.hip)
 int gmg_launch_tile_read(const uint64_t *d_off, uint64_t n_reads, uint64_t n_tiles, uint32_t *d_tile_read,

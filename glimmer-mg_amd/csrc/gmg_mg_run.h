@@ -31,10 +31,11 @@ static int mg_frame6_nulls(const gmg_model *gene, const float *d_null_tab, const
 {
     if (reads->total_bases == 0) return GMG_OK;
     const uint64_t gstride = (reads->total_bases + 15) & ~15ull;
+    GmgScratch sc(GmgScratch::AFTER, s);
     float *d_gene32 = nullptr;
-    GMG_HIP(gmg_pool_alloc((void **)&d_gene32, (size_t)6 * gstride * sizeof(float)));
-    int rc = mg_gene6_full(gene, groups, reads, d_gene32, gstride, s);
-    if (rc) { gmg_pool_release(d_gene32); return gmg_set_error(rc, "per-read null models need a gene model of the default shape (depth 7, window <= 15, periodicity 3)"); }
+    GMG_HIP(sc.alloc(&d_gene32, (size_t)6 * gstride * sizeof(float)));
+    const int rc = mg_gene6_full(gene, groups, reads, d_gene32, gstride, s);
+    if (rc) return gmg_set_error(rc, "per-read null models need a gene model of the default shape (depth 7, window <= 15, periodicity 3)");
     MgArgs a;
     memset(&a, 0, sizeof a);
     a.packed = reads->d_packed;
@@ -48,7 +49,6 @@ static int mg_frame6_nulls(const gmg_model *gene, const float *d_null_tab, const
     a.read_null = d_read_null;
     hipLaunchKernelGGL(k_mg_apply_nulls, dim3(grid_for(a.total)), dim3(256), 0, s, a, d_out, stride);
     GMG_HIP(hipGetLastError());
-    gmg_pool_release_after(d_gene32, s);
     return GMG_OK;
 }
 
@@ -65,14 +65,12 @@ extern "C" int gmg_frame_score6_nulls(const gmg_model *gene, const gmg_null_set 
             return gmg_set_error(GMG_ERANGE, "gmg_frame_score6_nulls: read %llu names null model %u of %d", (unsigned long long)r, read_null[r], nulls->n);
     if (reads->total_bases == 0) return GMG_OK;
     hipStream_t s = (hipStream_t)stream;
+    GmgScratch sc(GmgScratch::AFTER, s);
     uint32_t *d_rn = nullptr;
-    GMG_HIP(gmg_pool_alloc((void **)&d_rn, reads->n_reads * 4));
-    hipError_t e = hipMemcpyAsync(d_rn, read_null, reads->n_reads * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);              // (the caller's array may go away when the call returns)
-    int rc = e == hipSuccess ? mg_frame6_nulls(gene, nulls->d_tab, d_rn, reads, d_out, row_stride, s)
-                             : gmg_set_error(GMG_EHIP, "gmg_frame_score6_nulls: %s", hipGetErrorString(e));
-    gmg_pool_release_after(d_rn, s);
-    return rc;
+    GMG_HIP(sc.alloc(&d_rn, reads->n_reads * 4));
+    GMG_HIP(hipMemcpyAsync(d_rn, read_null, reads->n_reads * 4, hipMemcpyHostToDevice, s));
+    GMG_HIP(hipStreamSynchronize(s));                              // (the caller's array may go away when the call returns)
+    return mg_frame6_nulls(gene, nulls->d_tab, d_rn, reads, d_out, row_stride, s);
 }
 
 static unsigned mg_codon_from(const char *s)            // Codon_t::Set_From (gene.cc:133-146)

@@ -20,6 +20,7 @@
 
 #include <stdio.h>
 #include <string.h>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -307,6 +308,7 @@ extern "C" int gmg_model_set_load(const void *const *bytes, const uint64_t *n_by
     hipStream_t s = (hipStream_t)stream;
     gmg_model_set *set = new (std::nothrow) gmg_model_set();
     if (!set) return gmg_set_error(GMG_ENOMEM, "gmg_model_set_load: out of host memory");
+    std::unique_ptr<gmg_model_set> own(set);            // until the caller has it
     set->n = n_files;
     set->stream = s;
     set->d_block = nullptr;
@@ -331,14 +333,10 @@ extern "C" int gmg_model_set_load(const void *const *bytes, const uint64_t *n_by
         int param[6];
         char msg[200];
         const unsigned char *b = (const unsigned char *)bytes[k];
-        if (!header_info(b, n_bytes[k], param, msg, sizeof msg) || !shape_ok(param[2], param[3], param[4], param[5], msg, sizeof msg)) {
-            delete set;
+        if (!header_info(b, n_bytes[k], param, msg, sizeof msg) || !shape_ok(param[2], param[3], param[4], param[5], msg, sizeof msg))
             return gmg_set_error(GMG_EBADMODEL, "%s (file %d of the batch)", msg, k);
-        }
-        if (n_bytes[k] >= (1ull << 31) || (uint64_t)param[4] * param[5] >= (1ull << 31)) {
-            delete set;
+        if (n_bytes[k] >= (1ull << 31) || (uint64_t)param[4] * param[5] >= (1ull << 31))
             return gmg_set_error(GMG_EBADMODEL, "gmg_model_set_load: file %d of the batch is too large for the device loader (2 GiB, 2^31 slots)", k);
-        }
         set->bytes[k] = b;
         if (k && b != (const unsigned char *)bytes[k - 1] + n_bytes[k - 1]) contiguous = false;
         MsDesc &d = set->desc[k];
@@ -376,23 +374,19 @@ extern "C" int gmg_model_set_load(const void *const *bytes, const uint64_t *n_by
     memcpy(set->h_head.data(), set->desc.data(), (size_t)n_files * sizeof(MsDesc));
 
     // ---- device: everything queued on the caller's stream ----
-    unsigned char *scratch = nullptr;
-    hipError_t e = gmg_pool_alloc((void **)&set->d_block, blobs_end);
-    if (e == hipSuccess && (e = gmg_pool_alloc((void **)&scratch, sat)) != hipSuccess) gmg_pool_release(set->d_block);
-    if (e != hipSuccess) {
-        delete set;
-        return gmg_set_error(GMG_ENOMEM, "gmg_model_set_load: %zu + %zu bytes on the device: %s", blobs_end, sat, hipGetErrorString(e));
-    }
-    unsigned char *blk = set->d_block;
-#define MS_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (void)hipStreamSynchronize(s); gmg_pool_release(set->d_block); gmg_pool_release(scratch); delete set; \
-        return gmg_set_error(GMG_EHIP, "gmg_model_set_load: %s: %s", #call, hipGetErrorString(e_)); } } while (0)
-    MS_TRY(hipMemcpyAsync(blk, set->h_head.data(), head_bytes, hipMemcpyHostToDevice, s));
-    MS_TRY(hipMemsetAsync(blk + head_bytes, 0, blobs_end - head_bytes, s));
+    // (a failure waits for the stream before the blocks go back; on success the set takes the block and the staging block goes back
+    // once the kernels queued here have run)
+    GmgScratch sc(GmgScratch::STREAM, s);
+    unsigned char *blk = nullptr, *scratch = nullptr;
+    if (sc.alloc(&blk, blobs_end) != hipSuccess || sc.alloc(&scratch, sat) != hipSuccess)
+        return gmg_set_error(GMG_ENOMEM, "gmg_model_set_load: no device memory for %zu + %zu bytes", blobs_end, sat);
+    GMG_HIP(hipMemcpyAsync(blk, set->h_head.data(), head_bytes, hipMemcpyHostToDevice, s));
+    GMG_HIP(hipMemsetAsync(blk + head_bytes, 0, blobs_end - head_bytes, s));
     if (contiguous)
-        MS_TRY(hipMemcpyAsync(scratch, set->bytes[0], (size_t)(set->desc[n_files - 1].file_off + n_bytes[n_files - 1]), hipMemcpyHostToDevice, s));
+        GMG_HIP(hipMemcpyAsync(scratch, set->bytes[0], (size_t)(set->desc[n_files - 1].file_off + n_bytes[n_files - 1]), hipMemcpyHostToDevice, s));
     else
         for (int k = 0; k < n_files; k++)
-            MS_TRY(hipMemcpyAsync(scratch + set->desc[k].file_off, set->bytes[k], (size_t)n_bytes[k], hipMemcpyHostToDevice, s));
+            GMG_HIP(hipMemcpyAsync(scratch + set->desc[k].file_off, set->bytes[k], (size_t)n_bytes[k], hipMemcpyHostToDevice, s));
     uint32_t max_rec = 0;
     uint64_t max_fill = 0, max_flat = 0;
     for (const MsDesc &d : set->desc) {
@@ -409,26 +403,27 @@ extern "C" int gmg_model_set_load(const void *const *bytes, const uint64_t *n_by
     uint32_t *d_status = (uint32_t *)(blk + set->status_off), *d_flag = (uint32_t *)(scratch + flag_off), *d_pref = (uint32_t *)(scratch + pref_off);
     hipLaunchKernelGGL(k_ms_ids, dim3(grid_x(max_rec > max_fill ? max_rec : max_fill), n_files), dim3(MS_BLOCK), 0, s, d_desc, blk, scratch, d_flag,
                        d_status);
-    MS_TRY(hipGetLastError());
+    GMG_HIP(hipGetLastError());
     // (one entry more than there are records: pref[rec_base] of a last file without records is read too)
-    MS_TRY(hipMemsetAsync(d_flag + total_rec, 0, 16, s));
-    MS_TRY((gmg_scan_excl<uint32_t, uint32_t>(d_flag, d_pref, total_rec + 1, s)));
+    GMG_HIP(hipMemsetAsync(d_flag + total_rec, 0, 16, s));
+    GMG_HIP((gmg_scan_excl<uint32_t, uint32_t>(d_flag, d_pref, total_rec + 1, s)));
     hipLaunchKernelGGL(k_ms_parse, dim3(grid_x(max_rec), n_files), dim3(MS_BLOCK), 0, s, d_desc, blk, scratch, (const uint32_t *)d_flag,
                        (const uint32_t *)d_pref, d_status);
-    MS_TRY(hipGetLastError());
+    GMG_HIP(hipGetLastError());
     if (max_flat) {
         hipLaunchKernelGGL(k_ms_flatten, dim3(grid_x(max_flat), n_files), dim3(MS_BLOCK), 0, s, d_desc, blk);
-        MS_TRY(hipGetLastError());
+        GMG_HIP(hipGetLastError());
     }
-#undef MS_TRY
-    gmg_pool_release_after(scratch, s);
+    set->d_block = blk;
+    sc.detach(blk);
+    sc.wait = GmgScratch::AFTER;
     for (int k = 0; k < n_files; k++) {
         const MsDesc &d = set->desc[k];
         gmg_model &m = set->models[k];
         m.min_exp = 255; m.max_exp = 0; m.odd_values = 0;           // (known at _finish)
         gmg_model_bind(&m, blk + d.blob_off, d.W, d.D, d.P, d.N, lay[k]);
     }
-    *out = set;
+    *out = own.release();
     return GMG_OK;
 }
 

@@ -1098,6 +1098,16 @@ extern "C" int gmg_score_orfs_fetch(const gmg_orf_batch *b, gmg_orf_result *resu
     return GMG_OK;
 }
 
+// The batch's scratch comes on first use: a missing array is allocated straight into its field.  A batch that holds only some of
+// them is harmless: every array is tested on its own, and gmg_orf_batch_free frees whatever is there.
+template <class T> static hipError_t orf_lazy(T *&field, size_t bytes)
+{
+    if (field) return hipSuccess;
+    const hipError_t e = hipMalloc((void **)&field, bytes);
+    if (e != hipSuccess) field = nullptr;
+    return e;
+}
+
 extern "C" int gmg_score_orfs_begin(const gmg_model *gene, const gmg_model *nul, const gmg_reads *reads,
                                     const gmg_orf_batch *b, const gmg_orf_params *prm, uint64_t *out_n_starts, void *stream)
 {
@@ -1130,31 +1140,12 @@ extern "C" int gmg_score_orfs_begin(const gmg_model *gene, const gmg_model *nul,
     if (events) {
         const uint64_t head_words = reads->total_bases / 32 + 4;
         const uint64_t meta_stride = reads->total_bases / 8 + reads->n_reads + 64;
-        if (!mb->d_qpre) {
-            uint16_t *qp = nullptr;
-            uint8_t *qn = nullptr;
-            hipError_t e = hipMalloc((void **)&qp, (size_t)2 * meta_stride * 2);
-            if (e == hipSuccess) e = hipMalloc((void **)&qn, (size_t)2 * meta_stride);
-            if (e != hipSuccess) { if (qp) (void)hipFree(qp); return gmg_set_error(GMG_ENOMEM, "gmg_score_orfs: scratch: %s", hipGetErrorString(e)); }
-            mb->d_qpre = qp;
-            mb->d_qneed = qn;
-        }
-        if (!mb->d_gene6 || !mb->d_walk || !mb->d_heads) {
-            float *g6 = mb->d_gene6;
-            double *wk = mb->d_walk;
-            uint32_t *hd = mb->d_heads;
-            hipError_t e = g6 ? hipSuccess : hipMalloc((void **)&g6, (size_t)6 * reads->total_bases * sizeof(float));
-            if (e == hipSuccess && !wk) e = hipMalloc((void **)&wk, (size_t)2 * reads->total_bases * sizeof(double));
-            if (e == hipSuccess && !hd) e = hipMalloc((void **)&hd, (size_t)2 * head_words * 4);
-            if (e != hipSuccess) {
-                if (g6 && !mb->d_gene6) (void)hipFree(g6);
-                if (wk && !mb->d_walk) (void)hipFree(wk);
-                return gmg_set_error(GMG_ENOMEM, "gmg_score_orfs: scratch: %s", hipGetErrorString(e));
-            }
-            mb->d_gene6 = g6;
-            mb->d_walk = wk;
-            mb->d_heads = hd;
-        }
+        GMG_HIP(orf_lazy(mb->d_qpre, (size_t)2 * meta_stride * 2));
+        GMG_HIP(orf_lazy(mb->d_qneed, (size_t)2 * meta_stride));
+        // (eight spare entries: k_orf_walk_sums8 / 8p load a lane's eight values of every row without a predicate, up to entry 5 total + 7)
+        GMG_HIP(orf_lazy(mb->d_gene6, ((size_t)6 * reads->total_bases + 8) * sizeof(float)));
+        GMG_HIP(orf_lazy(mb->d_walk, ((size_t)2 * reads->total_bases + 8) * sizeof(double)));
+        GMG_HIP(orf_lazy(mb->d_heads, (size_t)2 * head_words * 4));
         int rc = gmg_launch_gene6(gene, reads, mb->d_gene6, s);
         if (rc) return gmg_set_error(rc, "gmg_score_orfs: gene-only pass refused the model");
         OrfWalkArgs wa;
@@ -1171,7 +1162,7 @@ extern "C" int gmg_score_orfs_begin(const gmg_model *gene, const gmg_model *nul,
         wa.q_pre = mb->d_qpre;
         wa.q_need = mb->d_qneed;
         wa.meta_stride = meta_stride;
-        // orfs_walk8 = 1 (default): Q only where k_orf_events can ask for it -- the ORFs' HEAD positions (marked here), start codons, the reads' ends;
+        // orfs_walk8 = 4 (default), 1 and 3: Q only where k_orf_events can ask for it -- the ORFs' HEAD positions (marked here), start codons, the reads' ends;
         // 2: every base (the form it is checked against); orfs_q_poison (tests): the array is filled with NaNs first, so that a read of an
         // entry that was not written cannot go unnoticed
         if (gmg_opt(GMG_OPT_ORFS_Q_POISON)) GMG_HIP(hipMemsetAsync(mb->d_walk, 0xff, (size_t)2 * reads->total_bases * sizeof(double), s));
@@ -1198,33 +1189,14 @@ extern "C" int gmg_score_orfs_begin(const gmg_model *gene, const gmg_model *nul,
         else hipLaunchKernelGGL(k_orf_walk_sums, dim3((unsigned)(wblocks < 256 * 64 ? wblocks : 256 * 64)), dim3(256), 0, s, wa);
         GMG_HIP(hipGetLastError());
     } else if (fused) {
-        if (!mb->d_gene6 || !mb->d_tmp) {                          // both or neither: a failed second allocation leaves nothing behind
-            float *g6 = mb->d_gene6;
-            OrfTmp *tmp = nullptr;
-            hipError_t e = g6 ? hipSuccess : hipMalloc((void **)&g6, (size_t)6 * reads->total_bases * sizeof(float));
-            if (e == hipSuccess) e = hipMalloc((void **)&tmp, (b->max_starts ? b->max_starts : 1) * sizeof(OrfTmp));
-            if (e != hipSuccess) {
-                if (g6 && !mb->d_gene6) (void)hipFree(g6);
-                return gmg_set_error(GMG_ENOMEM, "gmg_score_orfs: scratch: %s", hipGetErrorString(e));
-            }
-            mb->d_gene6 = g6;
-            mb->d_tmp = tmp;
-        }
+        GMG_HIP(orf_lazy(mb->d_gene6, ((size_t)6 * reads->total_bases + 8) * sizeof(float)));
+        GMG_HIP(orf_lazy(mb->d_tmp, (b->max_starts ? b->max_starts : 1) * sizeof(OrfTmp)));
         int rc = gmg_launch_gene6(gene, reads, mb->d_gene6, s);
         if (rc) return gmg_set_error(rc, "gmg_score_orfs: gene-only pass refused the model");
     } else {
         const size_t tl = b->segs->total_len;
-        if (!mb->d_score || !mb->d_indep) {
-            double *sc = nullptr, *in = nullptr;
-            hipError_t e = hipMalloc((void **)&sc, (tl ? tl : 1) * 8);
-            if (e == hipSuccess) e = hipMalloc((void **)&in, (tl ? tl : 1) * 8);
-            if (e != hipSuccess) {
-                if (sc) (void)hipFree(sc);
-                return gmg_set_error(GMG_ENOMEM, "gmg_score_orfs: scratch: %s", hipGetErrorString(e));
-            }
-            mb->d_score = sc;
-            mb->d_indep = in;
-        }
+        GMG_HIP(orf_lazy(mb->d_score, (tl ? tl : 1) * 8));
+        GMG_HIP(orf_lazy(mb->d_indep, (tl ? tl : 1) * 8));
         int rc = gmg_launch_seg_cum(gene, reads, b->segs, gene->dev.P == 1 ? 0 : 1, b->d_score, nullptr, s);
         if (rc) return rc;
         rc = gmg_launch_seg_cum(nul, reads, b->segs, nul->dev.P == 1 ? 0 : 1, b->d_indep, nullptr, s);

@@ -152,14 +152,13 @@ static hipError_t gmg_scan_excl(const TIn *d_in, TOut *d_out, uint64_t n, hipStr
 {
     if (n == 0) return hipSuccess;
     const uint64_t n_tiles = (n + SC_TILE - 1) / SC_TILE;
+    GmgScratch sc(GmgScratch::AFTER, s);
     uint64_t *d_sums = nullptr;
-    hipError_t e = gmg_pool_alloc((void **)&d_sums, n_tiles * 8);
+    const hipError_t e = sc.alloc(&d_sums, n_tiles * 8);
     if (e != hipSuccess) return e;
     const unsigned grid = (unsigned)(n_tiles < 256 * 16 ? n_tiles : 256 * 16);
     hipLaunchKernelGGL((k_scan_tile_sums<TIn>), dim3(grid), dim3(SC_BLOCK), 0, s, d_in, n, d_sums);
     hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, s, d_sums, n_tiles);
     hipLaunchKernelGGL((k_scan_apply<TIn, TOut>), dim3(grid), dim3(SC_BLOCK), 0, s, d_in, d_out, n, (const uint64_t *)d_sums);
-    e = hipGetLastError();
-    gmg_pool_release_after(d_sums, s);
-    return e;
+    return hipGetLastError();
 }

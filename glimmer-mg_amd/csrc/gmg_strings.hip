@@ -248,13 +248,13 @@ extern "C" int gmg_score_reads_strings(const gmg_model *const *models, int n_mod
     hipStream_t s = (hipStream_t)stream;
     const uint64_t nr = reads->n_reads;
     if (nr == 0 || n_models == 0) return GMG_OK;
+    GmgScratch sc(GmgScratch::STREAM, s);               // the scratch goes back to the cache once nothing queued may still use it
     float *d_vals = nullptr, *d_heads = nullptr;
     uint32_t *d_redo = nullptr;                         // [1 + 2 nr]: counter, list
-    gmg_segments *segs = nullptr;                       // built on demand for models without the fast pass
-    int rc = GMG_OK;
-    for (int k = 0; k < n_models && rc == GMG_OK; k++) {
+    struct Segs { gmg_segments *p = nullptr; ~Segs() { gmg_segments_free(p); } } segs;   // built on demand for models without the fast pass
+    for (int k = 0; k < n_models; k++) {
         const gmg_model *m = models[k];
-        if (!m) { rc = gmg_set_error(GMG_EINVAL, "gmg_score_reads_strings: model %d is NULL", k); break; }
+        if (!m) return gmg_set_error(GMG_EINVAL, "gmg_score_reads_strings: model %d is NULL", k);
         double *out = d_sums + (size_t)k * nr * 2;
         uint64_t tail_start = 0;
         // the fused form: values that are all <= 0 and not too small (ordinary reads then pass k_string_finish's test)
@@ -267,14 +267,12 @@ extern "C" int gmg_score_reads_strings(const gmg_model *const *models, int n_mod
         // with a zero probability (-FLT_MAX, exponent field 254; icm.cc:1345-1349) therefore takes the two-pass form.
         if (gmg_opt(GMG_OPT_STRINGS_FUSED) && !m->odd_values && m->min_exp >= 109 && m->max_exp - m->min_exp <= 23 &&
             reads->total_bases && reads->min_len >= 86) {
-            hipError_t e = hipMemsetAsync(out, 0, nr * 2 * sizeof(double), s);
-            if (e != hipSuccess) { rc = gmg_set_error(GMG_EHIP, "gmg_score_reads_strings: %s", hipGetErrorString(e)); break; }
+            GMG_HIP(hipMemsetAsync(out, 0, nr * 2 * sizeof(double), s));
             const int fused = gmg_launch_strings_sum(m, reads, out, &tail_start, s);
             if (fused == GMG_OK) {
-                if (!d_heads) e = gmg_pool_alloc((void **)&d_heads, (size_t)2 * nr * 16 * sizeof(float));
-                if (e == hipSuccess && !d_redo) e = gmg_pool_alloc((void **)&d_redo, (1 + 2 * nr) * sizeof(uint32_t));
-                if (e == hipSuccess) e = hipMemsetAsync(d_redo, 0, 4, s);
-                if (e != hipSuccess) { rc = gmg_set_error(GMG_ENOMEM, "gmg_score_reads_strings: %s", hipGetErrorString(e)); break; }
+                if (!d_heads) GMG_HIP(sc.alloc(&d_heads, (size_t)2 * nr * 16 * sizeof(float)));
+                if (!d_redo) GMG_HIP(sc.alloc(&d_redo, (1 + 2 * nr) * sizeof(uint32_t)));
+                GMG_HIP(hipMemsetAsync(d_redo, 0, 4, s));
                 StringFinishArgs f;
                 f.s.m = m->dev;
                 f.s.packed = reads->d_packed;
@@ -293,16 +291,12 @@ extern "C" int gmg_score_reads_strings(const gmg_model *const *models, int n_mod
                 const uint64_t fb = (2 * nr + 255) / 256;
                 hipLaunchKernelGGL(k_string_finish, dim3((unsigned)(fb < 256 * 32 ? fb : 256 * 32)), dim3(256), 0, s, f);
                 hipLaunchKernelGGL(k_string_exact, dim3(256 * 4), dim3(64), 0, s, f);
-                e = hipGetLastError();
-                if (e != hipSuccess) rc = gmg_set_error(GMG_EHIP, "gmg_score_reads_strings: %s", hipGetErrorString(e));
+                GMG_HIP(hipGetLastError());
                 continue;
             }
-            if (fused != GMG_EBADMODEL) { rc = fused; break; }
+            if (fused != GMG_EBADMODEL) return fused;
         }
-        if (!d_vals && reads->total_bases) {
-            hipError_t e = gmg_pool_alloc((void **)&d_vals, (size_t)2 * reads->total_bases * sizeof(float));
-            if (e != hipSuccess) { rc = gmg_set_error(GMG_ENOMEM, "gmg_score_reads_strings: %s", hipGetErrorString(e)); break; }
-        }
+        if (!d_vals && reads->total_bases) GMG_HIP(sc.alloc(&d_vals, (size_t)2 * reads->total_bases * sizeof(float)));
         const int fast = gmg_launch_strings(m, reads, d_vals, &tail_start, s);
         if (fast == GMG_OK) {
             StringSumArgs a;
@@ -314,10 +308,7 @@ extern "C" int gmg_score_reads_strings(const gmg_model *const *models, int n_mod
             a.tail_start = tail_start;
             a.vals = d_vals;
             a.sums = out;
-            if (!d_heads) {
-                hipError_t eh = gmg_pool_alloc((void **)&d_heads, (size_t)2 * nr * 16 * sizeof(float));
-                if (eh != hipSuccess) { rc = gmg_set_error(GMG_ENOMEM, "gmg_score_reads_strings: %s", hipGetErrorString(eh)); break; }
-            }
+            if (!d_heads) GMG_HIP(sc.alloc(&d_heads, (size_t)2 * nr * 16 * sizeof(float)));
             a.heads = d_heads;
             {
                 const uint64_t items = 2 * nr * (uint64_t)(m->dev.W - 1), hb = (items + 255) / 256;
@@ -325,32 +316,27 @@ extern "C" int gmg_score_reads_strings(const gmg_model *const *models, int n_mod
             }
             const uint64_t blocks = 2 * ((nr + STR_READS - 1) / STR_READS);
             hipLaunchKernelGGL(k_string_sum, dim3((unsigned)(blocks < 256 * 256 ? blocks : 256 * 256)), dim3(64), 0, s, a);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) rc = gmg_set_error(GMG_EHIP, "gmg_score_reads_strings: %s", hipGetErrorString(e));
+            GMG_HIP(hipGetLastError());
             continue;
         }
-        if (fast != GMG_EBADMODEL) { rc = fast; break; }
+        if (fast != GMG_EBADMODEL) return fast;
         // any other model shape: the exact segment kernel on (read, FORWARD) and (read, REVCOMP) segments
-        if (!segs) {
+        if (!segs.p) {
             std::vector<uint64_t> off(nr + 1);
-            hipError_t e = hipMemcpy(off.data(), reads->d_off, (nr + 1) * 8, hipMemcpyDeviceToHost);
-            if (e != hipSuccess) { rc = gmg_set_error(GMG_EHIP, "gmg_score_reads_strings: %s", hipGetErrorString(e)); break; }
+            GMG_HIP(hipMemcpy(off.data(), reads->d_off, (nr + 1) * 8, hipMemcpyDeviceToHost));
             std::vector<gmg_segment> sg(2 * nr);
             for (uint64_t r = 0; r < nr; r++) {
                 const uint32_t len = (uint32_t)(off[r + 1] - off[r]);
                 sg[2 * r] = {(uint32_t)r, 0, len, GMG_FORWARD};
                 sg[2 * r + 1] = {(uint32_t)r, 0, len, GMG_REVCOMP};
             }
-            rc = gmg_segments_upload(reads, sg.data(), 2 * nr, nullptr, nullptr, &segs);
-            if (rc) break;
+            const int rc = gmg_segments_upload(reads, sg.data(), 2 * nr, nullptr, nullptr, &segs.p);
+            if (rc) return rc;
         }
-        rc = gmg_score_string(m, reads, segs, 0, out, s);
+        const int rc = gmg_score_string(m, reads, segs.p, 0, out, s);
+        if (rc) return rc;
     }
-    hipError_t e = hipStreamSynchronize(s);            // the scratch goes back to the cache: nothing may still use it
-    if (d_vals) gmg_pool_release(d_vals);
-    if (d_heads) gmg_pool_release(d_heads);
-    if (d_redo) gmg_pool_release(d_redo);
-    if (segs) gmg_segments_free(segs);
-    if (rc == GMG_OK && e != hipSuccess) rc = gmg_set_error(GMG_EHIP, "gmg_score_reads_strings: %s", hipGetErrorString(e));
-    return rc;
+    GMG_HIP(hipStreamSynchronize(s));
+    sc.wait = GmgScratch::NONE;                         // (waited for just now)
+    return GMG_OK;
 }
