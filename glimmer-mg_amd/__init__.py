@@ -11,4 +11,5 @@ from . import shard as shard            # noqa: F401
 from .api import (ModelSet, icm_bytes_info, model_info, model_blob, model_value_stats, Icm, FixedIcm, FixedModel, fixed_score, Reads, NullSet, Segments, Trainer, init, frame_score6, segment_frame_score, segment_cumscore,  # noqa: F401
                   score_string, segment_partial_prob, all_frame_score, window_distrib, score_orfs, find_orfs, mg_score_reads, score_reads_strings, TopHits, GmgError,
                   FORWARD, REVERSED, COMPLEMENTED, REVCOMP, read_fasta, set_option, get_option, option,
-                  OrfResult, xlate_table, entropy_default_profiles, entropy_from_counts, entropy_regions, entropy_orfs)
+                  OrfResult, xlate_table, entropy_default_profiles, entropy_from_counts, entropy_regions, entropy_orfs,
+                  fasta_ambiguous, extract_plan, icm_train_reads, EXTRACT_REVERSED, COORD_USE_DIR, COORD_NOWRAP, COORD_SKIP_START, COORD_SKIP_STOP, COORD_MULTI)

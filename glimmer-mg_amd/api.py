@@ -152,6 +152,13 @@ class Icm:
         _ck(capi.lib().gmg_icm_train(arr, len(raw), model_len, model_depth, periodicity, C.byref(h)))
         return cls(h)
 
+    @classmethod
+    def train_reads(cls, reads, model_len=12, model_depth=7, periodicity=3):
+        """gmg_icm_train_reads: the same from training strings that already are a batch on the device (Reads.extract)"""
+        h = C.c_void_p()
+        _ck(capi.lib().gmg_icm_train_reads(reads.h, model_len, model_depth, periodicity, C.byref(h)))
+        return cls(h)
+
     @property
     def params(self):
         w, d, p, n = C.c_int(), C.c_int(), C.c_int(), C.c_int()
@@ -390,6 +397,24 @@ class Reads:
         sub.n_reads, sub.total_bases, sub.offsets = int(n.value), int(total.value), None
         return sub
 
+    def extract(self, regions, reversed=False, amb=None):
+        """gmg_reads_extract: a new device batch whose string k is region k = (read, first, len, strand) of this one, modulo its
+        read, strand < 0 downwards and complemented; reversed: every string back to front (build-icm -r); amb: (base indices,
+        codes) of fasta_ambiguous, the letters whose reverse-strand code is not the code complement"""
+        arr = (capi.GeneRegion * max(len(regions), 1))(*[capi.GeneRegion(int(r), int(f), int(ln), int(s)) for r, f, ln, s in regions])
+        base, code, n_amb = None, None, 0
+        if amb is not None and len(amb[0]):
+            base, code = np.ascontiguousarray(amb[0], np.uint64), np.ascontiguousarray(amb[1], np.uint8)
+            n_amb = len(base)
+        sub = Reads.__new__(Reads)
+        sub.h = C.c_void_p()
+        _ck(capi.lib().gmg_reads_extract(self.h, arr, len(regions), EXTRACT_REVERSED if reversed else 0,
+                                         _ptr(base) if n_amb else None, _ptr(code) if n_amb else None, n_amb, C.byref(sub.h)))
+        n, total = C.c_uint64(), C.c_uint64()
+        _ck(capi.lib().gmg_reads_info(sub.h, C.byref(n), C.byref(total)))
+        sub.n_reads, sub.total_bases, sub.offsets = int(n.value), int(total.value), None
+        return sub
+
     def close(self):
         if self.h:
             capi.lib().gmg_reads_free(self.h)
@@ -400,6 +425,37 @@ class Reads:
             self.close()
         except Exception:
             pass
+
+
+EXTRACT_REVERSED = 1                                    # GMG_EXTRACT_REVERSED
+COORD_USE_DIR, COORD_NOWRAP, COORD_SKIP_START, COORD_SKIP_STOP, COORD_MULTI = 1, 2, 4, 8, 16      # GMG_COORD_*
+
+
+def fasta_ambiguous(data):
+    """gmg_fasta_ambiguous (host): -> (base indices uint64, codes uint8) of the sequence bytes of a FASTA file outside acgtACGT:
+    where gmg_fasta_ingest puts them, and Subscript (Complement (byte))"""
+    data = bytes(data)
+    n = C.c_uint64()
+    _ck(capi.lib().gmg_fasta_ambiguous(data, len(data), None, None, 0, C.byref(n)))
+    base, code = np.zeros(max(n.value, 1), np.uint64), np.zeros(max(n.value, 1), np.uint8)
+    _ck(capi.lib().gmg_fasta_ambiguous(data, len(data), _ptr(base), _ptr(code), n.value, C.byref(n)))
+    return base[:n.value], code[:n.value]
+
+
+def extract_plan(offsets, coords, flags=0, min_len=0):
+    """gmg_extract_plan (host): coordinate lines (read, start, end[, dir]), 1-based inclusive, -> (regions [(read, first, len,
+    strand)], the line of every region) by extract's arithmetic, or multi-extract's with COORD_MULTI"""
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    arr = (capi.Coord * max(len(coords), 1))(*[capi.Coord(int(c[0]), int(c[3]) if len(c) > 3 else 0, int(c[1]), int(c[2])) for c in coords])
+    out = (capi.GeneRegion * max(len(coords), 1))()
+    line = np.zeros(max(len(coords), 1), np.uint64)
+    n = C.c_uint64()
+    _ck(capi.lib().gmg_extract_plan(_ptr(offsets), len(offsets) - 1, arr, len(coords), int(flags), int(min_len), out, _ptr(line), C.byref(n)))
+    return [(r.read, r.first, r.len, r.strand) for r in out[:n.value]], line[:n.value].copy()
+
+
+def icm_train_reads(reads, model_len=12, model_depth=7, periodicity=3):
+    return Icm.train_reads(reads, model_len, model_depth, periodicity)
 
 
 class Trainer:

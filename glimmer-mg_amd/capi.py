@@ -20,6 +20,10 @@ class GeneRegion(C.Structure):
     _fields_ = [("read", C.c_uint32), ("first", C.c_int32), ("len", C.c_int32), ("strand", C.c_int32)]
 
 
+class Coord(C.Structure):
+    _fields_ = [("read", C.c_uint32), ("dir", C.c_int32), ("start", C.c_int64), ("end", C.c_int64)]
+
+
 class MgGroup(C.Structure):
     _fields_ = [("gene", C.c_void_p), ("read_begin", C.c_uint64), ("read_end", C.c_uint64)]
 
@@ -77,6 +81,9 @@ PROTOTYPES = {
     "gmg_reads_info": (i32, [vp, C.POINTER(u64), C.POINTER(u64)]),
     "gmg_reads_download": (i32, [vp, vp, vp]),
     "gmg_reads_select": (i32, [vp, vp, u64, C.POINTER(vp)]),
+    "gmg_reads_extract": (i32, [vp, vp, u64, i32, vp, vp, u64, C.POINTER(vp)]),
+    "gmg_fasta_ambiguous": (i32, [C.c_char_p, u64, vp, vp, u64, C.POINTER(u64)]),
+    "gmg_extract_plan": (i32, [vp, u64, vp, u64, i32, C.c_int64, vp, vp, C.POINTER(u64)]),
     "gmg_single_create": (i32, [C.POINTER(vp)]),
     "gmg_single_stage": (i32, [vp, C.c_char_p, u64, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
     "gmg_single_fetch": (i32, [vp, vp, C.c_size_t]),
@@ -154,6 +161,7 @@ PROTOTYPES = {
     # include/gmg_icm.h
     "gmg_icm_new": (i32, [i32, i32, i32, C.POINTER(vp)]),
     "gmg_icm_train": (i32, [C.POINTER(C.c_char_p), i32, i32, i32, i32, C.POINTER(vp)]),
+    "gmg_icm_train_reads": (i32, [vp, i32, i32, i32, C.POINTER(vp)]),
     "gmg_icm_open": (i32, [C.c_char_p, C.POINTER(vp)]),
     "gmg_icm_build_indep": (i32, [vp, C.c_double, C.POINTER(C.c_char_p), i32]),
     "gmg_icm_write": (i32, [vp, C.c_char_p]),

@@ -48,6 +48,24 @@ extern "C" int  gmg_icm_train
    return  GMG_OK;
   }
 
+extern "C" int  gmg_icm_train_reads
+    (const gmg_reads * strings, int w, int d, int p, gmg_icm * * out)
+  {
+   if  (out == NULL || strings == NULL || w < 1 || d < 0 || d > 12 || p < 1)
+       return  gmg_set_error (GMG_EINVAL, "gmg_icm_train_reads: bad argument");
+   gmg_icm  * h = new (nothrow) gmg_icm (w, d, p);
+   if  (h == NULL)
+       return  gmg_set_error (GMG_ENOMEM, "gmg_icm_train_reads: out of memory");
+   string  err;
+   if  (! h -> model . Try_Train_Reads (strings, err))
+       {
+        delete  h;
+        return  gmg_set_error (GMG_EHIP, "%s", err . c_str ());
+       }
+   * out = h;
+   return  GMG_OK;
+  }
+
 extern "C" int  gmg_icm_open  (const char * path, gmg_icm * * out)
   {
    if  (path == NULL || out == NULL)

@@ -22,6 +22,7 @@
 #include <vector>
 
 struct gmg_model;   // include/gmg.h
+struct gmg_reads;
 struct gmg_fixed_model;
 
 // ---- constants of src/ICM/icm.hh:21-80 (callers and the training code use them) ----
@@ -172,6 +173,10 @@ class  ICM_Training_t  :  public ICM_t
    //  Train_Model without the exit: returns false and sets  err  when the device layer fails.
    bool  Try_Train_Model
        (const char * const * data, int string_ct, std::string & err);
+   //  the same from training strings that are already a batch on the device (gmg_reads_extract, gmg_reads_upload ...):
+   //  everything of Try_Train_Model behind its upload.   strings  stays the caller's.
+   bool  Try_Train_Reads
+       (const gmg_reads * strings, std::string & err);
   };
 
 

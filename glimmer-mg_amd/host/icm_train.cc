@@ -332,27 +332,9 @@ void  ICM_Training_t :: Train_Model
 bool  ICM_Training_t :: Try_Train_Model
     (const char * const * data, int string_ct, string & err)
   {
-   const int  npos = (model_len > 1 ? model_len - 1 : 1);
    gmg_reads  * strings = NULL;
-   gmg_trainer  * trainer = NULL;
-   bool  ok = false;
 
    Invalidate_Device_Mirror ();
-
-   //  GMG_TRAIN_TIMING=1: wall time of every stage on stderr
-   long long  timing_opt = 0;
-   gmg_get_option ("train_timing", & timing_opt);
-   const bool  timing = (timing_opt != 0);
-   chrono :: steady_clock :: time_point  t_prev = chrono :: steady_clock :: now ();
-   auto  lap = [&] (const char * what, int level)
-     {
-      if  (! timing)
-          return;
-      chrono :: steady_clock :: time_point  t = chrono :: steady_clock :: now ();
-      fprintf (stderr, "[gmg_train] %-10s level %2d %9.3f ms\n", what, level,
-               chrono :: duration <double, milli> (t - t_prev) . count ());
-      t_prev = t;
-     };
 
    {
     const char  * env = getenv ("GMG_DEVICE");
@@ -386,10 +368,7 @@ bool  ICM_Training_t :: Try_Train_Model
       ~ Words_t  ()  { free (p); }
       uint32_t  * data  (void)  { return  p; }
      }  packed (gmg_packed_words (off [string_ct]));
-   Table_Buffer_t  counts (size_t (periodicity) * (First_Node_Of_Level (model_depth + 1) - First_Node_Of_Level (model_depth))
-                             * npos * ALPHA_SQUARED);
-   vector <int16_t>  mip_prev;
-   if  (packed . p == NULL || counts . p == NULL)
+   if  (packed . p == NULL)
        {
         err = "ICM_Training_t::Train_Model: out of host memory";
         return  false;
@@ -412,8 +391,56 @@ bool  ICM_Training_t :: Try_Train_Model
          }
       }, 2, 1);
    }
-   if  (gmg_reads_upload (packed . data (), off . data (), string_ct, & strings) != GMG_OK
-          || gmg_trainer_create (strings, model_len, model_depth, periodicity, & trainer) != GMG_OK)
+   if  (gmg_reads_upload (packed . data (), off . data (), string_ct, & strings) != GMG_OK)
+       {
+        err = string ("ICM_Training_t::Train_Model: ") + gmg_last_error ();
+        return  false;
+       }
+   const bool  ok = Try_Train_Reads (strings, err);
+   gmg_reads_free (strings);
+   return  ok;
+  }
+
+
+bool  ICM_Training_t :: Try_Train_Reads
+    (const gmg_reads * strings, string & err)
+
+//  The training strings are a packed batch in HBM: the counting of every level on the device, the nodes' arithmetic
+//  on the host.   strings  is not freed.
+
+  {
+   const int  npos = (model_len > 1 ? model_len - 1 : 1);
+   gmg_trainer  * trainer = NULL;
+   bool  ok = false;
+
+   Invalidate_Device_Mirror ();
+
+   //  GMG_TRAIN_TIMING=1: wall time of every stage on stderr
+   long long  timing_opt = 0;
+   gmg_get_option ("train_timing", & timing_opt);
+   const bool  timing = (timing_opt != 0);
+   chrono :: steady_clock :: time_point  t_prev = chrono :: steady_clock :: now ();
+   auto  lap = [&] (const char * what, int level)
+     {
+      if  (! timing)
+          return;
+      chrono :: steady_clock :: time_point  t = chrono :: steady_clock :: now ();
+      fprintf (stderr, "[gmg_train] %-10s level %2d %9.3f ms\n", what, level,
+               chrono :: duration <double, milli> (t - t_prev) . count ());
+      t_prev = t;
+     };
+
+   Host_Workers_t  workers;
+   Table_Buffer_t  counts (size_t (periodicity) * (First_Node_Of_Level (model_depth + 1) - First_Node_Of_Level (model_depth))
+                             * npos * ALPHA_SQUARED);
+   vector <int16_t>  mip_prev;
+   if  (strings == NULL || counts . p == NULL)
+       {
+        err = (strings == NULL ? "ICM_Training_t::Train_Model: NULL training batch" : "ICM_Training_t::Train_Model: out of host memory");
+        return  false;
+       }
+
+   if  (gmg_trainer_create (strings, model_len, model_depth, periodicity, & trainer) != GMG_OK)
        goto  Fail;
    lap ("upload", -1);
 
@@ -517,7 +544,6 @@ bool  ICM_Training_t :: Try_Train_Model
    if  (! ok)
        err = string ("ICM_Training_t::Train_Model: ") + gmg_last_error ();
    gmg_trainer_free (trainer);
-   gmg_reads_free (strings);
    Invalidate_Device_Mirror ();
    return  ok;
   }

@@ -168,6 +168,48 @@ int gmg_reads_download(const gmg_reads *reads, uint32_t *packed2bit, uint64_t *b
  * null model of their classes (src/Glimmer/glimmer-mg.cc:361-375, 2050-2068) -- one gmg_mg_score_reads call per group. */
 int gmg_reads_select(const gmg_reads *reads, const uint64_t *idx, uint64_t n, gmg_reads **out);
 
+/* ---- regions of reads as a new batch: extract / multi-extract without the text (src/Util/extract.cc, multi-extract.cc) ----
+ * String k of *out is region k (a gmg_gene_region, declared with the entropy calls below, with the meaning they give it): `len`
+ * bases of read `read` from the 0-based `first`, read upwards (strand > 0) or downwards and complemented (strand < 0), positions
+ * modulo the read's length; empty regions give empty strings.  first in [0, read length), 0 <= len <= read length, strand != 0,
+ * read < n_reads: GMG_ERANGE naming the first bad region otherwise, and nothing is returned.  n = 0 gives a valid empty batch.
+ * GMG_EXTRACT_REVERSED: every string comes out back to front (what build-icm -r does to its input), in the same pass.
+ * The exceptions: on the reverse strand the reference prints Complement (letter) and the trainer takes Subscript of THAT, which is
+ * the code complement only for a c g t d h r y.  amb_base[0 .. n_amb): ascending job-wide base indices, in `reads`, of the bases
+ * whose letter is outside acgtACGT; amb_rev_code[i] = Subscript (Complement (letter)) (gmg_fasta_ambiguous makes both).  Where a
+ * strand < 0 region covers such a base the string holds amb_rev_code[i]; forward regions are never touched.  n_amb = 0 (NULL
+ * pointers): plain code complements.
+ * Null stream; returns when the batch is ready (as gmg_reads_select); free it with gmg_reads_free. */
+struct gmg_gene_region;
+#define GMG_EXTRACT_REVERSED 1
+int gmg_reads_extract(const gmg_reads *reads, const struct gmg_gene_region *regions, uint64_t n, int flags,
+                      const uint64_t *amb_base, const uint8_t *amb_rev_code, uint64_t n_amb, gmg_reads **out);
+/* host only.  Every sequence byte of `bytes` outside acgtACGT: its job-wide base index (as gmg_fasta_ingest numbers the bases)
+ * and Subscript (Complement (byte)) (src/Common/gene.cc:15-19, 1084-1091; src/ICM/icm.cc:2008-2027).  cap = room in both arrays;
+ * *n = how many there are (call with cap 0 to size); entries beyond cap are counted, not written. */
+int gmg_fasta_ambiguous(const char *bytes, uint64_t n_bytes, uint64_t *base, uint8_t *rev_code, uint64_t cap, uint64_t *n);
+/* Coordinate lines to regions: the arithmetic of extract (src/Util/extract.cc:84-149) or, with GMG_COORD_MULTI, multi-extract
+ * (src/Util/multi-extract.cc:131-173).  A gmg_coord is one parsed line: 1-based inclusive start and end on read `read`; dir is
+ * the line's direction field, used under GMG_COORD_USE_DIR (forward when > 0).  Without it a line is forward when
+ *   (start < end && (!circular || end - start <= L / 2)) || (circular && start - end > L / 2),   circular = !GMG_COORD_NOWRAP.
+ * Length 1 + |end - start| in the line's direction, plus L when negative; extract tests it against min_len before AND after the
+ * cuts of GMG_COORD_SKIP_START (3 bases off the start: the start moves up on the forward strand, DOWN on the reverse strand) and
+ * GMG_COORD_SKIP_STOP (3 off the end), multi-extract only after them.  A line that fails a test is skipped; a length below 0
+ * that passes gives an empty region, as the reference prints an empty record.
+ * regions / coord_of_region: room for n entries each (coord_of_region may be NULL); *n_regions of them are written, in the
+ * order of the lines, coord_of_region[k] = the line of region k.  base_offsets: the batch's n_reads + 1 offsets (HOST).
+ * GMG_ERANGE naming the line: a read index beyond n_reads, an empty sequence, a start that one wrap does not bring into [0, L)
+ * (the reference indexes outside its string there), a length above L (the reference walks round the circle again; this
+ * library refuses: INTEGRATION.md). */
+typedef struct gmg_coord { uint32_t read; int32_t dir; int64_t start, end; } gmg_coord;
+#define GMG_COORD_USE_DIR 1     /* extract -d   */
+#define GMG_COORD_NOWRAP 2      /* extract -w   */
+#define GMG_COORD_SKIP_START 4  /* extract -s   */
+#define GMG_COORD_SKIP_STOP 8   /* extract -t   */
+#define GMG_COORD_MULTI 16      /* multi-extract's order of the tests */
+int gmg_extract_plan(const uint64_t *base_offsets, uint64_t n_reads, const gmg_coord *coords, uint64_t n, int flags,
+                     int64_t min_len, struct gmg_gene_region *regions, uint64_t *coord_of_region, uint64_t *n_regions);
+
 /* ---- one string at a time ------------------------------------------------------
  * The ICM_t methods take ONE string per call (src/ICM/icm.hh:131-180).  A gmg_single keeps what such a call needs --
  * page-locked host staging, the packed read, its one segment and a result buffer on the device -- from call to call, so

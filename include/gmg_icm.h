@@ -29,6 +29,9 @@ int gmg_icm_free(gmg_icm *icm);
  * NUL-terminated lower-case strings (build-icm's Training_Data).  The counting runs on the device (gmg_trainer_*). */
 int gmg_icm_train(const char *const *strings, int n_strings, int model_len, int model_depth, int periodicity,
                   gmg_icm **out);
+/* the same from training strings that already are a batch on the device (gmg_reads_extract, gmg_reads_upload): string k is
+ * read k; nothing is packed or uploaded.  `strings` stays the caller's. */
+int gmg_icm_train_reads(const gmg_reads *strings, int model_len, int model_depth, int periodicity, gmg_icm **out);
 
 int gmg_icm_params(const gmg_icm *icm, int *model_len, int *model_depth, int *periodicity, int *num_nodes);
 /* copies mip[P*N] and prob4[P*N*4] (the layout gmg_model_upload takes) */
