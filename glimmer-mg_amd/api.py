@@ -442,6 +442,79 @@ def fasta_ambiguous(data):
     return base[:n.value], code[:n.value]
 
 
+def fasta_not_upper_acgt(data):
+    """gmg_fasta_not_upper_acgt (host): -> base indices uint64 of the sequence bytes of a FASTA file that are no upper-case ACGT"""
+    data = bytes(data)
+    n = C.c_uint64()
+    _ck(capi.lib().gmg_fasta_not_upper_acgt(data, len(data), None, 0, C.byref(n)))
+    base = np.zeros(max(n.value, 1), np.uint64)
+    _ck(capi.lib().gmg_fasta_not_upper_acgt(data, len(data), _ptr(base), n.value, C.byref(n)))
+    return base[:n.value]
+
+
+FEATURES_BLOCK, FEATURES_LENGTHS, FEATURES_STARTS, FEATURES_ORIENTS, FEATURES_DIST = 0, 1, 2, 3, 4     # GMG_FEATURES_*
+
+
+class FeatureTable:
+    """One table of train_features.py (GENE or NON) after destrand_orientations: lengths int64 [1 + largest bin], starts int64 [3]
+    (ATG GTG TTG), orient / orient_raw float64 [4] in the order (1,1) (1,-1) (-1,1) (-1,-1), dist: three float64 arrays, entry j the
+    bin of distance j - max_overlap (empty array: empty table)."""
+
+    def __init__(self, lengths, starts, orient, dist, orient_raw=None):
+        self.lengths = np.ascontiguousarray(lengths, np.int64)
+        self.starts = np.ascontiguousarray(starts, np.int64)
+        self.orient = np.ascontiguousarray(orient, np.float64)
+        self.orient_raw = np.ascontiguousarray(orient if orient_raw is None else orient_raw, np.float64)
+        self.dist = [np.ascontiguousarray(d, np.float64) for d in dist]
+
+    def _struct(self):
+        t = capi.FeaturesTable()
+        t.n_lengths = len(self.lengths)
+        t.lengths = self.lengths.ctypes.data_as(C.POINTER(C.c_int64)) if len(self.lengths) else None
+        for k in range(3):
+            t.starts[k] = int(self.starts[k])
+            t.n_dist[k] = len(self.dist[k])
+            t.dist[k] = self.dist[k].ctypes.data_as(C.POINTER(C.c_double)) if len(self.dist[k]) else None
+        for k in range(4):
+            t.orient[k] = float(self.orient[k])
+            t.orient_raw[k] = float(self.orient_raw[k])
+        return t
+
+
+def features_format(table, orf_type, what=FEATURES_BLOCK, max_overlap=50):
+    """gmg_features_format (host): the text of output_featurefile's block for one table, or the body of one of output_stats' files"""
+    t = table._struct()
+    n = C.c_size_t(0)
+    _ck(capi.lib().gmg_features_format(C.byref(t), orf_type.encode(), int(what), int(max_overlap), None, C.byref(n)))
+    buf = C.create_string_buffer(max(n.value, 1))
+    _ck(capi.lib().gmg_features_format(C.byref(t), orf_type.encode(), int(what), int(max_overlap), buf, C.byref(n)))
+    return buf.raw[:n.value].decode()
+
+
+def features_count(reads, genes, opaque=None, min_length=75, max_overlap=50, drop_tga=False, stream=None):
+    """gmg_features_count: genes = [(read, strand, start, end, start_codon)] grouped by read, clipped; opaque = ascending job-wide
+    indices of the bases that are no upper-case ACGT.  -> (GENE FeatureTable, NON FeatureTable, info dict)"""
+    arr = (capi.FeatureGene * max(len(genes), 1))(*[capi.FeatureGene(int(r), int(s), int(a), int(b), int(bool(sc))) for r, s, a, b, sc in genes])
+    n_opq = 0 if opaque is None else len(opaque)
+    opq = np.ascontiguousarray(opaque, np.uint64) if n_opq else None
+    prm = capi.FeaturesParams(int(min_length), int(max_overlap), int(bool(drop_tga)), 0)
+    h = C.c_void_p()
+    _ck(capi.lib().gmg_features_count(reads.h, arr, len(genes), _ptr(opq) if n_opq else None, n_opq, C.byref(prm), C.byref(h), stream))
+    try:
+        tables = []
+        for which in (0, 1):
+            t = capi.FeaturesTable()
+            _ck(capi.lib().gmg_features_fetch(h, which, C.byref(t)))
+            tables.append(FeatureTable(np.array(t.lengths[:t.n_lengths], np.int64), list(t.starts), list(t.orient),
+                                       [np.array(t.dist[k][:t.n_dist[k]], np.float64) for k in range(3)], list(t.orient_raw)))
+        n_units, n_rec = C.c_uint64(), C.c_uint64()
+        ms = np.zeros(8, np.float32)
+        _ck(capi.lib().gmg_features_info(h, C.byref(n_units), C.byref(n_rec), _ptr(ms)))
+    finally:
+        capi.lib().gmg_features_free(h)
+    return tables[0], tables[1], {"n_units": n_units.value, "n_records": n_rec.value, "stage_ms": ms[:5].copy(), "host_ms": ms[5:8].copy()}
+
+
 def extract_plan(offsets, coords, flags=0, min_len=0):
     """gmg_extract_plan (host): coordinate lines (read, start, end[, dir]), 1-based inclusive, -> (regions [(read, first, len,
     strand)], the line of every region) by extract's arithmetic, or multi-extract's with COORD_MULTI"""

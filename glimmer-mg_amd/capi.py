@@ -24,6 +24,19 @@ class Coord(C.Structure):
     _fields_ = [("read", C.c_uint32), ("dir", C.c_int32), ("start", C.c_int64), ("end", C.c_int64)]
 
 
+class FeatureGene(C.Structure):
+    _fields_ = [("read", C.c_uint32), ("strand", C.c_int32), ("start", C.c_int32), ("end", C.c_int32), ("start_codon", C.c_int32)]
+
+
+class FeaturesParams(C.Structure):
+    _fields_ = [("min_length", C.c_int32), ("max_overlap", C.c_int32), ("drop_tga", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FeaturesTable(C.Structure):
+    _fields_ = [("n_lengths", C.c_uint64), ("lengths", C.POINTER(C.c_int64)), ("starts", C.c_int64 * 3), ("orient", C.c_double * 4),
+                ("orient_raw", C.c_double * 4), ("n_dist", C.c_uint64 * 3), ("dist", C.POINTER(C.c_double) * 3)]
+
+
 class MgGroup(C.Structure):
     _fields_ = [("gene", C.c_void_p), ("read_begin", C.c_uint64), ("read_end", C.c_uint64)]
 
@@ -154,6 +167,12 @@ PROTOTYPES = {
     "gmg_tophits_scores": (i32, [vp, vp, i32, i32, vp, i32, vp, C.POINTER(vp)]),
     "gmg_tophits_fetch": (i32, [vp, vp, vp]),
     "gmg_tophits_format_rows": (i32, [vp, vp, i32, i32, vp, C.POINTER(C.c_size_t), vp]),
+    "gmg_features_count": (i32, [vp, vp, u64, vp, u64, vp, C.POINTER(vp), vp]),
+    "gmg_features_fetch": (i32, [vp, i32, vp]),
+    "gmg_features_info": (i32, [vp, C.POINTER(u64), C.POINTER(u64), vp]),
+    "gmg_features_free": (i32, [vp]),
+    "gmg_fasta_not_upper_acgt": (i32, [C.c_char_p, u64, vp, u64, C.POINTER(u64)]),
+    "gmg_features_format": (i32, [vp, C.c_char_p, i32, i32, vp, C.POINTER(C.c_size_t)]),
     "gmg_device_malloc": (i32, [C.POINTER(vp), C.c_size_t]),
     "gmg_device_free": (i32, [vp]),
     "gmg_memcpy_h2d": (i32, [vp, vp, C.c_size_t, vp]),

@@ -692,6 +692,70 @@ int gmg_tophits_fetch(const gmg_tophits *h, int64_t *keys, int32_t *models);
 int gmg_tophits_format_rows(gmg_tophits *h, const double *d_sums, int B, int forward_only, char *host_out, size_t *bytes,
                             void *stream);
 
+/* ---- feature models from predictions: scripts/train_features.py --predict P --seq S -----------------------
+ * After a run of the pipeline the reference retrains what the next run reads with -f: the length distributions of genes and of
+ * non-gene ORFs, the start-codon counts and the adjacent-orientation / adjacent-distance distributions (parse_genes,
+ * train_features.py:223-280; forward_parse_nongenes, :320-467, on every sequence and on its reverse complement;
+ * destrand_orientations, :544-554).  The non-gene side walks back from every stop codon of all six frames: that runs here.
+ * A gene is one line of the predict file as parse_predict (:163-199) leaves it: `read` in the batch, the sign of its frame
+ * field, the 0-based half-open [start, end) CLIPPED to the read (0 <= start, end <= length: GMG_ERANGE otherwise) and whether the
+ * end that holds its start codon lies inside the read.  The genes of a read are consecutive and keep the file's order; reads
+ * come in the order of their first gene line (the reference iterates a Python 2 dict: unspecified there); a read without genes
+ * takes no part at all.  opaque_base[0 .. n_opaque): the ascending job-wide indices of the bases whose letter is not an upper-case
+ * A C G T (gmg_fasta_not_upper_acgt): a codon with such a base is neither a start nor a stop on either strand.
+ * Integer counts are exact; every fractional bin is the sequential IEEE double sum of its 1.0 / num_starts terms in the reference's
+ * order (pass +1 before pass -1, reads in order, stops ascending with L, L + 1, L + 2 last, starts descending, the preceding gene
+ * before the succeeding one), bit for bit.
+ * GMG_ETOOBIG, never a truncated result: a read whose positions do not fit int32, more orientation / distance records than
+ * mg_max_entries (gmg_set_option).  Synchronises `stream`; the result lives on the host. */
+typedef struct gmg_feature_gene { uint32_t read; int32_t strand, start, end, start_codon; } gmg_feature_gene;
+typedef struct gmg_features_params {
+    int32_t min_length;          /* -l, default 75: shorter ORFs count in the length histogram only */
+    int32_t max_overlap;         /* -o, default 50; 0 .. 2^20                                       */
+    int32_t drop_tga;            /* -z: TGA is no stop codon                                        */
+    int32_t reserved;
+} gmg_features_params;
+/* One table (GENE or NON) after destrand_orientations.  lengths[l], l < n_lengths = 1 + the largest bin (0: none); starts in the
+ * order ATG GTG TTG; orient in the order (1,1) (1,-1) (-1,1) (-1,-1), orient_raw the four sums before destranding;
+ * dist[k][j], j < n_dist[k]: the bin of distance j - max_overlap under orientation k = (1,1) (1,-1) (-1,1), up to the largest
+ * bin present (n_dist[k] = 0: the table is empty).  The arrays belong to the handle (or, for gmg_features_format, the caller). */
+typedef struct gmg_features_table {
+    uint64_t n_lengths;
+    const int64_t *lengths;
+    int64_t starts[3];
+    double orient[4], orient_raw[4];
+    uint64_t n_dist[3];
+    const double *dist[3];
+} gmg_features_table;
+typedef struct gmg_features gmg_features;
+int gmg_features_count(const gmg_reads *reads, const gmg_feature_gene *genes, uint64_t n_genes, const uint64_t *opaque_base,
+                       uint64_t n_opaque, const gmg_features_params *params, gmg_features **out, void *stream);
+#define GMG_FEATURES_GENE 0
+#define GMG_FEATURES_NON 1
+int gmg_features_fetch(const gmg_features *f, int which, gmg_features_table *out);
+/* units of 32 positions the item kernels ran, orientation / distance records, and the time of the call's stages in ms (any pointer
+ * may be NULL).  Between events on the stream: [0] opaque bits + codon classes (with the uploads), [1] count pass, [2] scan, [3] write
+ * pass, [4] sorts + in-order sums.  On the host's clock: [5] the extents of the reads that have genes read back + the gene list, [6] from the first to the
+ * last of those events, [7] the histograms read back + destranding. */
+#define GMG_FEATURES_STAGES 8
+int gmg_features_info(const gmg_features *f, uint64_t *n_units, uint64_t *n_records, float *stage_ms);
+int gmg_features_free(gmg_features *f);
+/* host only.  The ascending job-wide indices (as gmg_fasta_ingest numbers the bases) of the sequence bytes of `bytes` that are not
+ * one of A C G T; counts and sizes as gmg_fasta_ambiguous does. */
+int gmg_fasta_not_upper_acgt(const char *bytes, uint64_t n_bytes, uint64_t *base, uint64_t cap, uint64_t *n);
+/* host only.  The text the script writes for one table: what = GMG_FEATURES_BLOCK the table's six sections of the feature file
+ * (output_featurefile, :630-673, titles with orf_type "GENE" / "NON"), or the body of one of output_stats' files (:562-623):
+ * _LENGTHS, _STARTS, _ORIENTS, _DIST + k.  Formats %d and %.1f, ranges from 0 (lengths) and -max_overlap (distances) to the largest
+ * bin, as there; an empty table prints no line (under -f the reference dies on an empty length table).
+ * *bytes: in = room at out, out = the length of the text (no terminator); out NULL only asks for the length, a smaller room is
+ * GMG_ERANGE. */
+#define GMG_FEATURES_BLOCK 0
+#define GMG_FEATURES_LENGTHS 1
+#define GMG_FEATURES_STARTS 2
+#define GMG_FEATURES_ORIENTS 3
+#define GMG_FEATURES_DIST 4
+int gmg_features_format(const gmg_features_table *t, const char *orf_type, int what, int max_overlap, char *out, size_t *bytes);
+
 /* ---- device memory helpers (for callers without their own allocator) -------- */
 int gmg_device_malloc(void **d_ptr, size_t bytes);
 int gmg_device_free(void *d_ptr);
