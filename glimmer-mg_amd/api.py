@@ -415,6 +415,21 @@ class Reads:
         sub.n_reads, sub.total_bases, sub.offsets = int(n.value), int(total.value), None
         return sub
 
+    def splice(self, runs, string_run_off, reversed=False):
+        """gmg_reads_splice: a new device batch whose string k is the concatenation of runs[string_run_off[k] : string_run_off[k + 1]],
+        a run = (read, first, len, kind) with kind one of RUN_UP, RUN_DOWN, RUN_SUB_UP, RUN_SUB_DOWN, RUN_LITERAL + code,
+        RUN_LITERAL_AS_IS + code; reversed: every string back to front"""
+        runs = np.ascontiguousarray(np.asarray(runs, np.uint32).reshape(-1, 4))
+        sro = np.ascontiguousarray(string_run_off, np.uint64)
+        sub = Reads.__new__(Reads)
+        sub.h = C.c_void_p()
+        _ck(capi.lib().gmg_reads_splice(self.h, _ptr(runs) if len(runs) else None, len(runs), _ptr(sro), len(sro) - 1,
+                                        EXTRACT_REVERSED if reversed else 0, C.byref(sub.h)))
+        n, total = C.c_uint64(), C.c_uint64()
+        _ck(capi.lib().gmg_reads_info(sub.h, C.byref(n), C.byref(total)))
+        sub.n_reads, sub.total_bases, sub.offsets = int(n.value), int(total.value), None
+        return sub
+
     def close(self):
         if self.h:
             capi.lib().gmg_reads_free(self.h)
@@ -429,6 +444,32 @@ class Reads:
 
 EXTRACT_REVERSED = 1                                    # GMG_EXTRACT_REVERSED
 COORD_USE_DIR, COORD_NOWRAP, COORD_SKIP_START, COORD_SKIP_STOP, COORD_MULTI = 1, 2, 4, 8, 16      # GMG_COORD_*
+
+
+RUN_UP, RUN_DOWN, RUN_SUB_UP, RUN_SUB_DOWN, RUN_LITERAL, RUN_LITERAL_AS_IS = 0, 1, 2, 3, 4, 8      # GMG_RUN_*
+
+
+def edits_plan(offsets, genes, odd=None):
+    """gmg_edits_plan (host): the gene lines of a predict file -- (read, column 2, column 3, frame, insertions, deletions,
+    substitutions), positions 1-based as written, in file order -- to the strings extract_aa.py prints: -> (runs uint32 [n, 4],
+    string_run_off uint64, strings [(line, start, end, strand, pad_front, pad_behind)]).  odd: (base indices, letters) of the
+    bases whose letter is no upper-case A C G T"""
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    arr = (capi.EditGene * max(len(genes), 1))(*[capi.EditGene(int(g[0]), int(g[3]), int(g[1]), int(g[2]), len(g[4]), len(g[5]), len(g[6]), 0)
+                                                  for g in genes])
+    pos = np.array([p for g in genes for lst in g[4:7] for p in lst] + [0], np.int64)
+    odd_base, odd_letter, n_odd = None, None, 0
+    if odd is not None and len(odd[0]):
+        odd_base, odd_letter, n_odd = np.ascontiguousarray(odd[0], np.uint64), bytes(odd[1]), len(odd[0])
+    strings = (capi.EditString * max(len(genes), 1))()
+    sro = np.zeros(len(genes) + 1, np.uint64)
+    n = C.c_uint64()
+    args = (_ptr(offsets), len(offsets) - 1, arr, len(genes), _ptr(pos), _ptr(odd_base) if n_odd else None, odd_letter, n_odd)
+    _ck(capi.lib().gmg_edits_plan(*args, None, 0, C.byref(n), _ptr(sro), strings))
+    runs = np.zeros((max(n.value, 1), 4), np.uint32)
+    _ck(capi.lib().gmg_edits_plan(*args, _ptr(runs), n.value, C.byref(n), _ptr(sro), strings))
+    rows = [(int(s.gene), int(s.start), int(s.end), int(s.strand), int(s.pad_front), int(s.pad_behind)) for s in strings[:len(genes)]]
+    return runs[:n.value], sro, rows
 
 
 def fasta_ambiguous(data):

@@ -24,6 +24,20 @@ class Coord(C.Structure):
     _fields_ = [("read", C.c_uint32), ("dir", C.c_int32), ("start", C.c_int64), ("end", C.c_int64)]
 
 
+class SpliceRun(C.Structure):
+    _fields_ = [("read", C.c_uint32), ("first", C.c_uint32), ("len", C.c_uint32), ("kind", C.c_uint32)]
+
+
+class EditGene(C.Structure):
+    _fields_ = [("read", C.c_uint32), ("frame", C.c_int32), ("col2", C.c_int64), ("col3", C.c_int64), ("n_ins", C.c_uint32),
+                ("n_del", C.c_uint32), ("n_sub", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class EditString(C.Structure):
+    _fields_ = [("gene", C.c_uint64), ("start", C.c_int64), ("end", C.c_int64), ("strand", C.c_int32), ("pad_front", C.c_uint32),
+                ("pad_behind", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class FeatureGene(C.Structure):
     _fields_ = [("read", C.c_uint32), ("strand", C.c_int32), ("start", C.c_int32), ("end", C.c_int32), ("start_codon", C.c_int32)]
 
@@ -97,6 +111,8 @@ PROTOTYPES = {
     "gmg_reads_extract": (i32, [vp, vp, u64, i32, vp, vp, u64, C.POINTER(vp)]),
     "gmg_fasta_ambiguous": (i32, [C.c_char_p, u64, vp, vp, u64, C.POINTER(u64)]),
     "gmg_extract_plan": (i32, [vp, u64, vp, u64, i32, C.c_int64, vp, vp, C.POINTER(u64)]),
+    "gmg_reads_splice": (i32, [vp, vp, u64, vp, u64, i32, C.POINTER(vp)]),
+    "gmg_edits_plan": (i32, [vp, u64, vp, u64, vp, vp, C.c_char_p, u64, vp, u64, C.POINTER(u64), vp, vp]),
     "gmg_single_create": (i32, [C.POINTER(vp)]),
     "gmg_single_stage": (i32, [vp, C.c_char_p, u64, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
     "gmg_single_fetch": (i32, [vp, vp, C.c_size_t]),

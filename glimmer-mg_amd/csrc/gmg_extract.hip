@@ -17,6 +17,7 @@
 
 #include "gmg_internal.h"
 
+#include "gmg_piece.h"
 #include "gmg_scan.h"
 
 #include <string.h>
@@ -83,29 +84,6 @@ __global__ __launch_bounds__(256) void k_ext_len(const uint64_t *src_off, const 
         if (over) atomicAdd(&stats[2], over);
         if (bad != ~0ull) atomicMin(&stats[4], bad);
     }
-}
-
-// nb (1 .. 16) bases of a read whose base 0 is job-wide base S, from position p on, as 2-bit codes from bit 0: upwards p, p + 1, ...
-// or downwards p, p - 1, ...  The caller keeps the piece inside the read; what the window holds beyond it (the neighbouring
-// reads' bases, the guard words) is masked out here.
-__device__ __forceinline__ uint32_t ext_piece(const uint32_t *__restrict__ src, uint64_t S, uint32_t p, bool down, bool comp, unsigned nb)
-{
-    uint32_t x;
-    if (!down) {
-        const uint64_t sg = S + p;
-        const uint64_t w0 = sg >> 4;
-        x = (uint32_t)(((uint64_t)src[w0] | ((uint64_t)src[w0 + 1] << 32)) >> (2u * (unsigned)(sg & 15)));
-    } else {
-        // the 16 bases that END at S + p (word -1 is the guard in front of the batch): base S + p lands in the top two bits;
-        // bit reversal turns the order of the bases AND of the two bits of every base, the second of which is undone
-        const int64_t lo = (int64_t)(S + p) - 15;
-        const int64_t w0 = lo >> 4;
-        x = (uint32_t)(((uint64_t)src[w0] | ((uint64_t)src[w0 + 1] << 32)) >> (2u * (unsigned)(lo & 15)));
-        x = __brev(x);
-        x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
-    }
-    if (comp) x ^= 0xffffffffu;
-    return x & (nb >= 16 ? 0xffffffffu : ((1u << (2 * nb)) - 1u));
 }
 
 // One wave per 1,024-base tile of the NEW batch, a lane per 16-base word (k_reads_select's shape).  The strings that overlap the

@@ -210,6 +210,69 @@ typedef struct gmg_coord { uint32_t read; int32_t dir; int64_t start, end; } gmg
 int gmg_extract_plan(const uint64_t *base_offsets, uint64_t n_reads, const gmg_coord *coords, uint64_t n, int flags,
                      int64_t min_len, struct gmg_gene_region *regions, uint64_t *coord_of_region, uint64_t *n_regions);
 
+/* ---- strings spliced from several pieces of a read: scripts/extract_aa.py without the text -------------------------------
+ * What glimmer-mg's retraining loop needs under -i / -s: the gene strings with every predicted insertion, deletion and
+ * substitution applied to the read (train_features.py --indels = extract_aa.py | build-icm -r).
+ *
+ * gmg_reads_splice: string k of *out is the concatenation of runs[string_run_off[k] .. string_run_off[k + 1]) (HOST arrays;
+ * string_run_off ascends from 0 to n_runs).  A run is `len` bases of read `read` of `reads`:
+ *   GMG_RUN_UP        positions first, first + 1, ...                     codes as they are
+ *   GMG_RUN_DOWN      positions first, first - 1, ...                     3 - code
+ *   GMG_RUN_SUB_UP    as UP, every code replaced by the script's substitution on codes: c -> g, anything else -> c
+ *   GMG_RUN_SUB_DOWN  as DOWN, the substitution first, then 3 - code
+ *   GMG_RUN_LITERAL + c, GMG_RUN_LITERAL_AS_IS + c (c = 0 .. 3): `len` times the code c; read and first are not looked at (the
+ *                     plan leaves the base the literal stands for in them; AS_IS tells a caller that prints letters that the
+ *                     letter there is printed as it is -- the script's rc() on a letter outside ATCGatcg)
+ * Nothing wraps: an upward run needs first + len <= read length, a downward one len <= first + 1 and first < read length (any
+ * first <= read length when len = 0); read < n_reads, kind one of the above: GMG_ERANGE naming the first bad run otherwise, and
+ * nothing is returned.  Empty strings and empty runs are fine; n_strings = 0 gives a valid empty batch.
+ * GMG_EXTRACT_REVERSED: every string comes out back to front (build-icm -r), in the same pass.
+ * Null stream; returns when the batch is ready (as gmg_reads_extract); free it with gmg_reads_free. */
+typedef struct gmg_splice_run { uint32_t read, first, len, kind; } gmg_splice_run;
+#define GMG_RUN_UP 0
+#define GMG_RUN_DOWN 1
+#define GMG_RUN_SUB_UP 2
+#define GMG_RUN_SUB_DOWN 3
+#define GMG_RUN_LITERAL 4
+#define GMG_RUN_LITERAL_AS_IS 8
+int gmg_reads_splice(const gmg_reads *reads, const gmg_splice_run *runs, uint64_t n_runs, const uint64_t *string_run_off,
+                     uint64_t n_strings, int flags, gmg_reads **out);
+/* host only.  The edit arithmetic of scripts/extract_aa.py: the gene lines of a predict file to the runs of their strings.
+ * genes[0 .. n_genes): the lines in file order (the lines of one read need not be adjacent; their order is what counts): read,
+ * the second and third column, the frame column (forward when > 0) and how many I: / D: / S: positions the line lists;
+ * positions: those lists back to back -- line 0's insertions, deletions, substitutions, then line 1's -- as written (1-based).
+ * odd_base / odd_letter (n_odd may be 0): the ascending job-wide indices of the bases whose letter is not an upper-case A C G T
+ * (gmg_fasta_not_upper_acgt) and those letters; with them the runs hold literals where the rules on codes differ from the
+ * script's rules on letters (a substitution on any such letter gives C; rc() complements acgt and leaves any other letter).
+ * What the script does, restated:
+ *   get_preds     the shift of a read, sum of (deletions - insertions listed) over its lines in file order, moves a line's start
+ *                 by the sum in front of the line and its end by the sum including it; start = column 2 - 1, end = column 3 on
+ *                 the forward strand, start = column 3 - 1, end = column 2 on the reverse strand.  The lines of a read are then
+ *                 sorted by start, stably.
+ *   predict_msa   one step per base f = 0, 1, ... of the read against the three sorted lists of ALL lines of the read, a cursor
+ *                 each; the first of insertion, deletion, substitution whose cursor stands at f wins and only that cursor
+ *                 moves (a cursor that is passed -- a position listed twice, or taken by a list of higher priority, or below
+ *                 1 -- never moves again; positions beyond the read never fire).  An insertion drops base f.  A deletion
+ *                 puts out what the step before put out once more (nothing after a dropped base, a pad blank at f = 0), then
+ *                 base f.  A substitution puts out G for the letter C and C for any other letter.  Three pad blanks in front;
+ *                 three behind and one more for every listed deletion that did not fire.
+ *   print_frag_genes   s counts the corrected characters from -3.  Forward: inside [start, start + 3) the frame restarts and
+ *                 the string begins at s = start >= 0; inside [end - 3, end) the walk is switched off; elsewhere, while switched
+ *                 on, the string grows once begun, and begins at the first s >= 0 on a codon boundary.  Reverse: [start,
+ *                 start + 3) switches the walk on without output, [end - 3, end) switches it off and adds every character that
+ *                 is no blank, elsewhere as forward.  The string is cut to a multiple of three characters, blanks counted,
+ *                 and a reverse string is then reversed and complemented.
+ * Output, room for n_genes entries each: strings[j] for the j-th record the script prints -- reads ascending, the lines of a
+ * read by adjusted start -- with the line it came from, start and end as the record name shows them, the strand, and the
+ * blanks in front of and behind the printed string (pads never become runs); string_run_off[n_genes + 1]; runs[0 .. *n_runs).
+ * runs_cap = room in runs; runs beyond it are counted, not written (call with 0 to size).
+ * GMG_ERANGE naming the line: a read index beyond n_reads, a read of 2^31 bases or more. */
+typedef struct gmg_edit_gene { uint32_t read; int32_t frame; int64_t col2, col3; uint32_t n_ins, n_del, n_sub, reserved; } gmg_edit_gene;
+typedef struct gmg_edit_string { uint64_t gene; int64_t start, end; int32_t strand; uint32_t pad_front, pad_behind, reserved; } gmg_edit_string;
+int gmg_edits_plan(const uint64_t *base_offsets, uint64_t n_reads, const gmg_edit_gene *genes, uint64_t n_genes,
+                   const int64_t *positions, const uint64_t *odd_base, const char *odd_letter, uint64_t n_odd,
+                   gmg_splice_run *runs, uint64_t runs_cap, uint64_t *n_runs, uint64_t *string_run_off, gmg_edit_string *strings);
+
 /* ---- one string at a time ------------------------------------------------------
  * The ICM_t methods take ONE string per call (src/ICM/icm.hh:131-180).  A gmg_single keeps what such a call needs --
  * page-locked host staging, the packed read, its one segment and a result buffer on the device -- from call to call, so

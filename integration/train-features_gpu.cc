@@ -12,7 +12,7 @@
 //  Sequences are taken in the order of their first gene line in P; the script iterates a Python 2 dict there, so the order of
 //  its additions -- and with it the last bits of its fractional bins -- is not defined by the reference.
 //  Not here: --gbk (needs Biopython), --rbs and the .motif file (need ELPH), --indels (extract_aa.py): each is refused with
-//  status 2.  A sequence header that occurs twice, a predict header without a sequence, a gene line with fewer than four fields
+//  status 2 (the gene ICM of --indels is extract-aa_gpu --gicm, integration/extract-aa_gpu.cc).  A sequence header that occurs twice, a predict header without a sequence, a gene line with fewer than four fields
 //  and an input without any gene line end the run with status 1 and a message that names them.  <prefix>.gene.fasta is not
 //  written.
 
