@@ -867,6 +867,51 @@ def entropy_orfs(reads, orf_result, aa, pos, neg, want_counts=True, want_dist=Tr
         reads.h, orf_result.h, aa, _ptr(pos), _ptr(neg), c, d, None))
 
 
+AUDIT_NEXT_STOP = 1                                     # GMG_AUDIT_NEXT_STOP
+GENE_AUDIT_DTYPE = np.dtype([("first_codon", "<i4"), ("last_codon", "<i4"), ("start_which", "<i4"), ("stop_which", "<i4"),
+                             ("n_inner_stops", "<i4"), ("inner_begin", "<u4"), ("last_back_stop", "<i4"), ("next_stop", "<i4")])
+
+
+def audit_params(start_codons=("atg", "gtg", "ttg"), stop_codons=DEFAULT_STOPS, flags=AUDIT_NEXT_STOP):
+    """a gmg_audit_params; the codons go in as they are given (the library refuses all but lower-case acgt triplets)"""
+    prm = capi.AuditParams()
+    prm.n_start_codons, prm.n_stop_codons, prm.flags = len(start_codons), len(stop_codons), int(flags)
+    for dst, lst in ((prm.start_codon, start_codons), (prm.stop_codon, stop_codons)):
+        for i, c in enumerate(lst[:8]):
+            dst[i].value = (c.encode() if isinstance(c, str) else bytes(c))[:4]
+    return prm
+
+
+def _region_array(regions):
+    """regions as the bytes of a gmg_gene_region array: an int array [n, 4] as it is, a list of (read, first, len, strand) rows"""
+    arr = np.ascontiguousarray(np.asarray(regions, np.int64).reshape(-1, 4).astype(np.int32))
+    return arr, len(arr)
+
+
+def genes_audit(reads, regions, start_codons=("atg", "gtg", "ttg"), stop_codons=DEFAULT_STOPS, flags=AUDIT_NEXT_STOP, amb=None,
+                stream=None, fetch=True):
+    """gmg_genes_audit: regions = [(read, first, len, strand)] (or an int array [n, 4]); amb = ascending job-wide indices of the
+    bases whose letter is outside acgtACGT.  -> (records GENE_AUDIT_DTYPE [n], inner int32 [n_inner], hist int64 [65]); fetch=False:
+    only (n_regions, n_inner), nothing copied back"""
+    arr, n = _region_array(regions)
+    n_amb = 0 if amb is None else len(amb)
+    ab = np.ascontiguousarray(amb, np.uint64) if n_amb else None
+    prm = audit_params(start_codons, stop_codons, flags)
+    h = C.c_void_p()
+    _ck(capi.lib().gmg_genes_audit(reads.h, _ptr(arr) if n else None, n, C.byref(prm), _ptr(ab) if n_amb else None, n_amb, C.byref(h), stream))
+    try:
+        nr, ni = C.c_uint64(), C.c_uint64()
+        _ck(capi.lib().gmg_audit_info(h, C.byref(nr), C.byref(ni)))
+        if not fetch:
+            _ck(capi.lib().gmg_synchronize(stream))
+            return nr.value, ni.value
+        rec, inner, hist = np.zeros(max(nr.value, 1), GENE_AUDIT_DTYPE), np.zeros(max(ni.value, 1), np.int32), np.zeros(65, np.int64)
+        _ck(capi.lib().gmg_audit_fetch(h, _ptr(rec), _ptr(inner), _ptr(hist)))
+    finally:
+        capi.lib().gmg_audit_free(h)
+    return rec[:nr.value], inner[:ni.value], hist
+
+
 START_ERRORS_DTYPE = np.dtype([("pos", "<i4", (2,)), ("type", "i1", (2,)), ("n", "i1"), ("reserved", "i1")])
 MG_ACCEPTED_ONLY, MG_ALLOW_INDELS, MG_ALLOW_SUBS = 1, 2, 4
 

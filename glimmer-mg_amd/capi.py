@@ -51,6 +51,11 @@ class FeaturesTable(C.Structure):
                 ("orient_raw", C.c_double * 4), ("n_dist", C.c_uint64 * 3), ("dist", C.POINTER(C.c_double) * 3)]
 
 
+class AuditParams(C.Structure):
+    _fields_ = [("n_start_codons", C.c_int32), ("n_stop_codons", C.c_int32), ("start_codon", (C.c_char * 4) * 8),
+                ("stop_codon", (C.c_char * 4) * 8), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 class MgGroup(C.Structure):
     _fields_ = [("gene", C.c_void_p), ("read_begin", C.c_uint64), ("read_end", C.c_uint64)]
 
@@ -170,6 +175,10 @@ PROTOTYPES = {
     "gmg_entropy_orfs": (i32, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "gmg_entropy_from_counts": (i32, [vp, vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gmg_entropy_default_profiles": (i32, [vp, vp]),
+    "gmg_genes_audit": (i32, [vp, vp, u64, vp, vp, u64, C.POINTER(vp), vp]),
+    "gmg_audit_info": (i32, [vp, C.POINTER(u64), C.POINTER(u64)]),
+    "gmg_audit_fetch": (i32, [vp, vp, vp, vp]),
+    "gmg_audit_free": (i32, [vp]),
     "gmg_trainer_create": (i32, [vp, i32, i32, i32, C.POINTER(vp)]),
     "gmg_trainer_level_counts": (i32, [vp, i32, vp, vp]),
     "gmg_trainer_free": (i32, [vp]),

@@ -702,6 +702,47 @@ int gmg_entropy_from_counts(const int32_t counts[20], const double pos[20], cons
 /* DEFAULT_POS_ENTROPY_PROF / DEFAULT_NEG_ENTROPY_PROF (src/Common/gene.hh:47-52) */
 int gmg_entropy_default_profiles(double pos[20], double neg[20]);
 
+/* ---- gene coordinates audited: anomaly and start-codon-distrib without the text ------------------------
+ * What src/Glimmer/anomaly.cc:76-240 and src/Util/start-codon-distrib.cc:84-106 look at in every gene of a coordinate list, for a
+ * batch of regions in one call.  A region is a gmg_gene_region with the meaning gmg_entropy_regions gives it: `len` bases of read
+ * `read` from the 0-based `first`, upwards (strand > 0) or downwards and complemented (strand < 0), positions modulo THAT read's
+ * length; offsets below count bases of the region in its reading direction.  A codon is named by 16*b0 + 4*b1 + b2 (a=0 c=1 g=2
+ * t=3) of its three bases in reading direction.
+ * The reference compares raw lower-cased letters with strncmp (anomaly.cc:254-286), no IUPAC matching: amb_base[0 .. n_amb) are the
+ * ascending job-wide indices of the bases whose letter is outside acgtACGT (gmg_fasta_ambiguous's indices; NULL with n_amb = 0), and
+ * a codon that holds one matches no pattern and has the code -1.
+ * Every output is an integer: there is no tolerance. */
+typedef struct gmg_audit_params {
+    int32_t n_start_codons, n_stop_codons;          /* 0 .. 8 each */
+    char start_codon[8][4], stop_codon[8][4];       /* three lower-case letters of a c g t and a NUL; anything else: GMG_EINVAL */
+    int32_t flags;                                  /* GMG_AUDIT_NEXT_STOP */
+    int32_t reserved;
+} gmg_audit_params;
+#define GMG_AUDIT_NEXT_STOP 1   /* fill next_stop for the regions whose last codon is no stop codon */
+typedef struct gmg_gene_audit {
+    int32_t first_codon, last_codon;  /* the region's first / last three bases; -1: len < 3, or one of them is in amb_base */
+    int32_t start_which, stop_which;  /* index in start_codon of the first codon / in stop_codon of the last codon (the first of equal
+                                         patterns); -1 none */
+    int32_t n_inner_stops;            /* stop codons at offsets i = 0, 3, 6, ... with i < len - 3 (anomaly.cc:190-192, 224-231) */
+    uint32_t inner_begin;             /* their offsets: inner[inner_begin .. inner_begin + n_inner_stops), ascending */
+    int32_t last_back_stop;           /* the largest i of len - 6, len - 9, ..., i >= 0, whose codon is a stop; -1 none (anomaly.cc:209-211) */
+    int32_t next_stop;                /* the smallest j of len, len + 3, ..., j < read length, whose codon (offsets j .. j + 2, modulo the
+                                         read) is a stop; -1: none, or not asked for, or the last codon is a stop (anomaly.cc:157-176) */
+} gmg_gene_audit;
+typedef struct gmg_audit gmg_audit;
+/* regions: HOST array, any order, repeats allowed.  first in [0, read length), 0 <= len <= read length, strand != 0, read < n_reads,
+ * a read of fewer than 2^31 bases: GMG_ERANGE naming the first bad region otherwise, and nothing is returned.  n = 0 gives a valid
+ * empty result.  More inner stops in total than mg_max_entries (gmg_set_option): GMG_ETOOBIG, never a truncated list.
+ * Stream-ordered; the call itself waits once for the count pass (the size of the list).  The result lives on the device until
+ * gmg_audit_fetch, which synchronises the stream the call ran on; free the handle before that stream is destroyed. */
+int gmg_genes_audit(const gmg_reads *reads, const struct gmg_gene_region *regions, uint64_t n, const gmg_audit_params *params,
+                    const uint64_t *amb_base, uint64_t n_amb, gmg_audit **out, void *stream);
+int gmg_audit_info(const gmg_audit *a, uint64_t *n_regions, uint64_t *n_inner);
+/* HOST arrays, any may be NULL: records[n_regions], inner[n_inner], first_codon_hist[c] = the number of regions with first_codon ==
+ * c, bin 64 those with -1 (counted on the device in the same call). */
+int gmg_audit_fetch(const gmg_audit *a, gmg_gene_audit *records, int32_t *inner, int64_t first_codon_hist[65]);
+int gmg_audit_free(gmg_audit *a);
+
 /* ---- build-icm: training counts on the device ---------------------------------------
  * Replaces the counting of ICM_Training_t: Count_Char_Pairs for the roots (src/ICM/icm.cc:1841-1870, called from
  * Train_Model, icm.cc:1373-1390), Count_Char_Pairs_Restricted + Get_Training_Node for every deeper level
