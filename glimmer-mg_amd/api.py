@@ -912,6 +912,68 @@ def genes_audit(reads, regions, start_codons=("atg", "gtg", "ttg"), stop_codons=
     return rec[:nr.value], inner[:ni.value], hist
 
 
+def window_counts(reads, window_len, window_skip, amb=None, stream=None, fetch=True, device=False):
+    """gmg_window_counts: the {a, c, g, t, other} counts of every window of every read; amb = ascending job-wide indices of the bases
+    whose letter is outside acgtACGT.  -> (read_window_off uint64 [n_reads + 1], counts int32 [n_windows, 5]); fetch=False: only
+    (n_reads, n_windows), nothing copied back; device=True: the rows are also read back through the pointers of gmg_windows_device
+    and returned as a third and fourth value"""
+    n_amb = 0 if amb is None else len(amb)
+    ab = np.ascontiguousarray(amb, np.uint64) if n_amb else None
+    h = C.c_void_p()
+    _ck(capi.lib().gmg_window_counts(reads.h, int(window_len), int(window_skip), _ptr(ab) if n_amb else None, n_amb, C.byref(h), stream))
+    try:
+        nr, nw = C.c_uint64(), C.c_uint64()
+        _ck(capi.lib().gmg_windows_info(h, C.byref(nr), C.byref(nw)))
+        if not fetch:
+            _ck(capi.lib().gmg_synchronize(stream))
+            return nr.value, nw.value
+        off, counts = np.zeros(nr.value + 1, np.uint64), np.zeros((max(nw.value, 1), 5), np.int32)
+        _ck(capi.lib().gmg_windows_fetch(h, _ptr(off), _ptr(counts)))
+        if device:
+            d_off, d_counts = C.c_void_p(), C.c_void_p()
+            _ck(capi.lib().gmg_windows_device(h, C.byref(d_off), C.byref(d_counts)))
+            off2, counts2 = np.zeros(nr.value + 1, np.uint64), np.zeros((max(nw.value, 1), 5), np.int32)
+            _ck(capi.lib().gmg_memcpy_d2h(_ptr(off2), d_off, off2.nbytes, stream))
+            if nw.value:
+                _ck(capi.lib().gmg_memcpy_d2h(_ptr(counts2), d_counts, nw.value * 20, stream))
+            _ck(capi.lib().gmg_synchronize(stream))
+            return off, counts[:nw.value], off2, counts2[:nw.value]
+    finally:
+        capi.lib().gmg_windows_free(h)
+    return off, counts[:nw.value]
+
+
+def regions_uncovered(reads, intervals, min_len=0, stream=None, fetch=True):
+    """gmg_regions_uncovered: intervals = [(read, lo, hi)], 0-based half open, any order -> (gaps int32 [n_gaps, 4] = rows (read, first,
+    len, +1), ready for Reads.extract / entropy_regions / genes_audit; read_gap_off uint64 [n_reads + 1]); fetch=False: only n_gaps"""
+    arr = np.ascontiguousarray(np.asarray(intervals, np.int64).reshape(-1, 3).astype(np.uint32).view(np.int32))
+    n = len(arr)
+    h = C.c_void_p()
+    _ck(capi.lib().gmg_regions_uncovered(reads.h, _ptr(arr) if n else None, n, int(min_len), C.byref(h), stream))
+    try:
+        ng = C.c_uint64()
+        _ck(capi.lib().gmg_gaps_info(h, C.byref(ng)))
+        if not fetch:
+            _ck(capi.lib().gmg_synchronize(stream))
+            return ng.value
+        gaps, off = np.zeros((max(ng.value, 1), 4), np.int32), np.zeros(reads.n_reads + 1, np.uint64)
+        _ck(capi.lib().gmg_gaps_fetch(h, _ptr(gaps), _ptr(off)))
+    finally:
+        capi.lib().gmg_gaps_free(h)
+    return gaps[:ng.value], off
+
+
+def uncovered_plan(offsets, coords, flags=0):
+    """gmg_uncovered_plan (host): coordinate lines (read, start, end[, dir]), 1-based inclusive, -> [(read, lo, hi)] by uncovered's
+    arithmetic (a line that runs over the sequence's end gives two)"""
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    arr = (capi.Coord * max(len(coords), 1))(*[capi.Coord(int(c[0]), int(c[3]) if len(c) > 3 else 0, int(c[1]), int(c[2])) for c in coords])
+    out = np.zeros((max(2 * len(coords), 1), 3), np.int32)
+    n = C.c_uint64()
+    _ck(capi.lib().gmg_uncovered_plan(_ptr(offsets), len(offsets) - 1, arr, len(coords), int(flags), _ptr(out), C.byref(n)))
+    return [(int(r), int(a), int(b)) for r, a, b in out[:n.value]]
+
+
 START_ERRORS_DTYPE = np.dtype([("pos", "<i4", (2,)), ("type", "i1", (2,)), ("n", "i1"), ("reserved", "i1")])
 MG_ACCEPTED_ONLY, MG_ALLOW_INDELS, MG_ALLOW_SUBS = 1, 2, 4
 

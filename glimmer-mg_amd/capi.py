@@ -179,6 +179,16 @@ PROTOTYPES = {
     "gmg_audit_info": (i32, [vp, C.POINTER(u64), C.POINTER(u64)]),
     "gmg_audit_fetch": (i32, [vp, vp, vp, vp]),
     "gmg_audit_free": (i32, [vp]),
+    "gmg_window_counts": (i32, [vp, C.c_int64, C.c_int64, vp, u64, C.POINTER(vp), vp]),
+    "gmg_windows_info": (i32, [vp, C.POINTER(u64), C.POINTER(u64)]),
+    "gmg_windows_fetch": (i32, [vp, vp, vp]),
+    "gmg_windows_device": (i32, [vp, C.POINTER(vp), C.POINTER(vp)]),
+    "gmg_windows_free": (i32, [vp]),
+    "gmg_regions_uncovered": (i32, [vp, vp, u64, C.c_int64, C.POINTER(vp), vp]),
+    "gmg_gaps_info": (i32, [vp, C.POINTER(u64)]),
+    "gmg_gaps_fetch": (i32, [vp, vp, vp]),
+    "gmg_gaps_free": (i32, [vp]),
+    "gmg_uncovered_plan": (i32, [vp, u64, vp, u64, i32, vp, C.POINTER(u64)]),
     "gmg_trainer_create": (i32, [vp, i32, i32, i32, C.POINTER(vp)]),
     "gmg_trainer_level_counts": (i32, [vp, i32, vp, vp]),
     "gmg_trainer_free": (i32, [vp]),

@@ -743,6 +743,59 @@ int gmg_audit_info(const gmg_audit *a, uint64_t *n_regions, uint64_t *n_inner);
 int gmg_audit_fetch(const gmg_audit *a, gmg_gene_audit *records, int32_t *inner, int64_t first_codon_hist[65]);
 int gmg_audit_free(gmg_audit *a);
 
+/* ---- window composition and uncovered regions: window-acgt and uncovered without the text ----------------
+ * gmg_window_counts: what src/Util/window-acgt.cc:63-137 counts (Subscript, :233-252) for every window of every read of a batch.
+ * A read of L bases has, with W = window_len and S = window_skip (the reference's ring buffer worked out):
+ *   L = 0               no window
+ *   0 < L < W           one window, the whole read
+ *   L >= W              the full windows at the 0-based offsets 0, S, .. , k S with k = (L - W) / S, and, when (L - W) % S != 0
+ *                       and (k + 1) S < L, ONE more from (k + 1) S to the read's end; nothing after it
+ * Window j of read r is row read_window_off[r] + j; it starts at offset j S and is min (W, L - j S) bases long, which is why neither
+ * is stored.  A row is {a, c, g, t, other}: `other` = the bases of the window that are in amb_base[0 .. n_amb), the ascending
+ * job-wide indices of the bases whose letter is outside acgtACGT (gmg_fasta_ambiguous's indices; NULL with n_amb = 0); the four
+ * letter counts cover the rest (the code the packed batch holds at a listed base is taken off again).
+ * window_len < 1 or window_skip < 1: GMG_EINVAL; a list that does not ascend strictly or reaches total_bases: GMG_EINVAL; a read
+ * of 2^31 bases or more: GMG_ERANGE; more windows than mg_max_entries (gmg_set_option): GMG_ETOOBIG, never a truncated table.
+ * reads: a device batch; amb_base: HOST.  Stream-ordered; the call itself waits once for the number of windows.  The result lives
+ * on the device until gmg_windows_fetch, which synchronises the stream the call ran on; free the handle before that stream is
+ * destroyed.  Every output is an integer: there is no tolerance. */
+typedef struct gmg_windows gmg_windows;
+int gmg_window_counts(const gmg_reads *reads, int64_t window_len, int64_t window_skip, const uint64_t *amb_base, uint64_t n_amb,
+                      gmg_windows **out, void *stream);
+int gmg_windows_info(const gmg_windows *w, uint64_t *n_reads, uint64_t *n_windows);
+/* HOST arrays, either may be NULL: read_window_off[n_reads + 1], counts[n_windows][5] */
+int gmg_windows_fetch(const gmg_windows *w, uint64_t *read_window_off, int32_t *counts);
+/* the same two arrays where they are: DEVICE pointers, valid until gmg_windows_free, written in the order of the call's stream */
+int gmg_windows_device(const gmg_windows *w, const uint64_t **d_read_window_off, const int32_t **d_counts);
+int gmg_windows_free(gmg_windows *w);
+
+/* gmg_regions_uncovered: Coalesce_Regions + Output_Uncovered (src/Util/uncovered.cc:186-288): the stretches of every read that none
+ * of the intervals covers.  Per read the intervals are taken in ascending lo with the running maximum of hi: a gap [a, b) lies in
+ * front of every interval whose lo exceeds the maximum so far (a = that maximum, 0 at the read's start, b = lo), one more runs from
+ * the final maximum to the read's end.  A gap is kept when len > 0 && len >= min_len.  A read without intervals gives the gap
+ * [0, L), an empty read none; touching intervals merge; an empty interval inside a gap splits it.
+ * Gaps come out as gmg_gene_region {read, first = a, len = b - a, strand = +1}, by read and then ascending: gaps[read_gap_off[r] ..
+ * read_gap_off[r + 1]) are read r's.
+ * intervals: HOST array, any order.  0 <= lo <= hi <= read length and read < n_reads, every read shorter than 2^31 bases:
+ * GMG_ERANGE naming the first bad interval otherwise, and nothing is returned.  n = 0 is valid.  More gaps than mg_max_entries:
+ * GMG_ETOOBIG.  Stream-ordered; the call itself waits once for the number of gaps; gmg_gaps_fetch synchronises that stream. */
+typedef struct gmg_interval { uint32_t read; int32_t lo, hi; } gmg_interval;   /* 0-based, half open: bases lo .. hi - 1 of read `read` */
+typedef struct gmg_gaps gmg_gaps;
+int gmg_regions_uncovered(const gmg_reads *reads, const gmg_interval *intervals, uint64_t n, int64_t min_len, gmg_gaps **out,
+                          void *stream);
+int gmg_gaps_info(const gmg_gaps *g, uint64_t *n_gaps);
+/* HOST arrays, either may be NULL: gaps[n_gaps], read_gap_off[n_reads + 1] */
+int gmg_gaps_fetch(const gmg_gaps *g, struct gmg_gene_region *gaps, uint64_t *read_gap_off);
+int gmg_gaps_free(gmg_gaps *g);
+/* host only.  Coordinate lines to intervals: the arithmetic of uncovered (src/Util/uncovered.cc:87-174) on gmg_coord lines under the
+ * GMG_COORD_USE_DIR / NOWRAP / SKIP_START / SKIP_STOP flags of gmg_extract_plan.  Unlike that planner there is no length test, a
+ * region that runs over the sequence's end (the start, on the reverse strand) becomes TWO intervals, and the reverse strand's i =
+ * start, j = i - extract_len give [j, i).  intervals: room for 2 n entries; *n_intervals of them are written, in the order of the
+ * lines.  GMG_ERANGE naming the line: a read index beyond n_reads, a read of 2^31 bases or more, and every line at which the
+ * reference's own arithmetic leaves 0 <= lo <= hi <= L (it prints from outside its string there). */
+int gmg_uncovered_plan(const uint64_t *base_offsets, uint64_t n_reads, const gmg_coord *coords, uint64_t n, int flags,
+                       gmg_interval *intervals, uint64_t *n_intervals);
+
 /* ---- build-icm: training counts on the device ---------------------------------------
  * Replaces the counting of ICM_Training_t: Count_Char_Pairs for the roots (src/ICM/icm.cc:1841-1870, called from
  * Train_Model, icm.cc:1373-1390), Count_Char_Pairs_Restricted + Get_Training_Node for every deeper level
