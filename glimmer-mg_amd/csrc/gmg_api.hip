@@ -3,6 +3,7 @@
 // No CPU fallback: without a gfx950 device every scoring entry point fails loudly.
 
 #include "gmg_internal.h"
+#include "gmg_gather.h"
 #include "gmg_scan.h"
 
 #include <ctype.h>
@@ -618,92 +619,94 @@ extern "C" int gmg_reads_wrap_device(const uint32_t *d_packed, const uint64_t *d
     return GMG_OK;
 }
 
+// ---- batches built on the device out of another batch (gmg_gather.h): the host steps around the caller's kernels
+int GmgBatchBuilder::begin()
+{
+    const unsigned long long stats0[6] = {~0ull, 0, 0, 0, ~0ull, 0};
+    GMG_HIP(sc.alloc(&d_stats, 8 * sizeof(unsigned long long)));
+    GMG_HIP(hipMemcpyAsync(d_stats, stats0, sizeof stats0, hipMemcpyHostToDevice, s));
+    return GMG_OK;
+}
+
+int GmgBatchBuilder::lengths(const uint64_t *d_total)
+{
+    GMG_HIP(hipGetLastError());
+    GMG_HIP(hipMemcpyAsync(&stats[5], d_total, 8, hipMemcpyDeviceToHost, s));
+    GMG_HIP(hipMemcpyAsync(stats, d_stats, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    GMG_HIP(hipStreamSynchronize(s));
+    return GMG_OK;
+}
+
+int GmgBatchBuilder::layout(uint64_t n, uint64_t *d_off)
+{
+    // the packed words: the guards are zeroed here, every data word is the gather's to write
+    total = stats[5];
+    data_words = (total + 15) / 16;
+    uint32_t *alloc = nullptr;
+    GMG_HIP(sc.alloc(&alloc, (data_words + 2 * GMG_GUARD_WORDS) * 4));
+    GMG_HIP(hipMemsetAsync(alloc, 0, GMG_GUARD_WORDS * 4, s));
+    GMG_HIP(hipMemsetAsync(alloc + GMG_GUARD_WORDS + data_words, 0, GMG_GUARD_WORDS * 4, s));
+    d_words = alloc + GMG_GUARD_WORDS;
+    tmp.n_reads = n;
+    tmp.total_bases = total;
+    tmp.d_off = d_off;
+    tmp.owns_off = 1;
+    tmp.n_words = data_words + GMG_GUARD_WORDS;
+    tmp.d_packed_alloc = alloc;
+    tmp.d_packed = d_words;
+    return gmg_reads_tile_table(&tmp, sc, s);
+}
+
+int GmgBatchBuilder::finish(const char *who, gmg_reads **out)
+{
+    GMG_HIP(hipGetLastError());
+    GMG_HIP(hipStreamSynchronize(s));
+    gmg_reads_set_lengths(&tmp, stats);
+    gmg_reads *r = new (std::nothrow) gmg_reads(tmp);
+    if (!r) return gmg_set_error(GMG_ENOMEM, "%s: out of host memory", who);
+    sc.detach(tmp.d_off); sc.detach(tmp.d_packed_alloc); sc.detach(tmp.d_tile_read);
+    sc.wait = GmgScratch::NONE;                         // (waited for just now)
+    *out = r;
+    return GMG_OK;
+}
+
 // ---- gmg_reads_select: everything on the device (a chunk of glimmer-mg's classification mode gathers all of its reads into
 // visiting order: 1 M reads per call) -- lengths by index, offsets by a scan, the gather itself through the new batch's tile
 // table, the batch's length statistics by a reduction; what crosses PCIe is the index list and 48 bytes back.
-// stats: [0] min length, [1] max length, [2] reads over 512 bases, [3] unused, [4] first bad index
 __global__ __launch_bounds__(256) void k_sel_len(const uint64_t *src_off, const uint64_t *idx, uint64_t n, uint64_t n_src, uint64_t *len,
                                                  unsigned long long *stats)
 {
-    // few blocks, a grid-stride loop: the four results of a WAVE go to the counters with one atomic each (every atomic on one
-    // address costs ~10 ns at the L2: one per wave of a million reads was 0.36 ms)
-    unsigned long long mn = ~0ull, mx = 0, over = 0, bad = ~0ull;
+    GmgLenStats st;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += (uint64_t)gridDim.x * blockDim.x) {
         uint64_t l = 0;
         if (i < n) {
             const uint64_t r = idx[i];
-            if (r >= n_src) bad = i < bad ? i : bad;
+            if (r >= n_src) st.bad_item(i);
             else l = src_off[r + 1] - src_off[r];
-            mn = l < mn ? l : mn;
-            mx = l > mx ? l : mx;
-            over += l > 512;
+            st.length(l);
         }
         len[i] = l;                                     // len[n] = 0: the scan's last output is the total
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long a = __shfl_xor(mn, o), b = __shfl_xor(mx, o), c = __shfl_xor(bad, o);
-        mn = a < mn ? a : mn;
-        mx = b > mx ? b : mx;
-        bad = c < bad ? c : bad;
-        over += __shfl_xor(over, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (mn != ~0ull) atomicMin(&stats[0], mn);
-        if (mx) atomicMax(&stats[1], mx);
-        if (over) atomicAdd(&stats[2], over);
-        if (bad != ~0ull) atomicMin(&stats[4], bad);
-    }
+    st.finish(stats);
 }
 
-// One wave per 1,024-base tile of the NEW batch (64 lanes x one 16-base word): the reads that overlap the tile -- the first one
-// from the tile table, their ends and source positions fetched ONCE by the wave's first lanes into LDS -- then a lane builds its
-// word from one 32-base window of the source per read that overlaps it (mostly one, two at a read boundary): no global load
-// depends on another one except through LDS.
-#define SEL_R 32                                        // reads of a tile handled through LDS; further ones (tiles of many tiny reads) by the lane itself
+// a read of the new batch is ONE stretch of the source, upwards: mostly one piece per word, two at a read boundary
+struct SelSource {
+    static constexpr uint32_t R = 32;
+    struct Item { uint64_t src; };                      // source index of the read's base 0 minus its new begin (mod 2^64)
+    const uint32_t *src;
+    const uint64_t *src_off, *idx;
+    __device__ __forceinline__ Item stage(uint64_t r, uint64_t beg) const { return Item{src_off[idx[r]] - beg}; }
+    __device__ __forceinline__ uint32_t piece(const Item &it, uint64_t pos, unsigned &nb) const
+    {
+        return ext_piece(src, it.src + pos, 0, false, false, nb);
+    }
+};
+
 __global__ __launch_bounds__(256) void k_reads_select(const uint32_t *src, const uint64_t *src_off, const uint64_t *idx, const uint64_t *new_off,
                                                       const uint32_t *tile_read, uint64_t n, uint64_t total, uint32_t *dst)
 {
-    __shared__ uint64_t s_end[4][SEL_R], s_src[4][SEL_R];     // per wave: end of read r0 + k in the new batch; source position of its base 0 minus its new begin
-    const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint64_t n_tiles = (total + GMG_TILE - 1) / GMG_TILE;
-    for (uint64_t t = (uint64_t)blockIdx.x * 4 + wv; t < n_tiles; t += (uint64_t)gridDim.x * 4) {
-        const uint64_t r0 = tile_read[t];
-        if (lane < SEL_R) {
-            const uint64_t r = r0 + lane < n ? r0 + lane : n - 1;
-            const uint64_t b = new_off[r], e = r0 + lane < n ? new_off[r + 1] : ~0ull;
-            s_end[wv][lane] = e;
-            s_src[wv][lane] = src_off[idx[r]] - b;     // source index of new base g of this read = s_src + g (mod 2^64)
-        }
-        __builtin_amdgcn_wave_barrier();
-        const uint64_t g0 = t * GMG_TILE + 16 * (uint64_t)lane;
-        if (g0 < total) {
-            const uint64_t g1 = g0 + 16 < total ? g0 + 16 : total;
-            uint32_t k = 0, out = 0;
-            uint64_t pos = g0;
-            while (pos < g1) {
-                while (k < SEL_R && s_end[wv][k] <= pos) k++;          // the read that holds base pos (empty reads are stepped over)
-                if (k >= SEL_R) break;
-                const uint64_t e = s_end[wv][k] < g1 ? s_end[wv][k] : g1;
-                const uint64_t sg = s_src[wv][k] + pos;
-                const uint64_t w0 = sg >> 4;
-                const unsigned sh = 2u * (unsigned)(sg & 15);
-                const uint64_t x = ((uint64_t)src[w0] | ((uint64_t)src[w0 + 1] << 32)) >> sh;      // bases pos .. pos + 15 of that read
-                const unsigned nb = (unsigned)(e - pos);                                            // 1 .. 16 of them count
-                out |= ((uint32_t)x & (nb >= 16 ? 0xffffffffu : ((1u << (2 * nb)) - 1u))) << (2u * (unsigned)(pos - g0));
-                pos = e;
-            }
-            if (pos < g1) {                             // beyond the reads in LDS: base by base
-                uint64_t r = r0 + SEL_R - 1;
-                for (; pos < g1; pos++) {
-                    while (new_off[r + 1] <= pos) r++;
-                    const uint64_t sg = src_off[idx[r]] + (pos - new_off[r]);
-                    out |= ((src[sg >> 4] >> (2u * (unsigned)(sg & 15))) & 3u) << (2u * (unsigned)(pos - g0));
-                }
-            }
-            dst[t * (GMG_TILE / 16) + lane] = out;
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
+    gmg_gather_tiles(SelSource{src, src_off, idx}, new_off, tile_read, n, total, dst);
 }
 
 extern "C" int gmg_reads_select(const gmg_reads *reads, const uint64_t *idx, uint64_t n, gmg_reads **out)
@@ -712,53 +715,23 @@ extern "C" int gmg_reads_select(const gmg_reads *reads, const uint64_t *idx, uin
     if (!reads || (!idx && n) || !out || n >= 0x7ffffffeull) return gmg_set_error(GMG_EINVAL, "gmg_reads_select: bad argument");
     hipStream_t s = 0;
     GmgScratch sc(GmgScratch::STREAM, s);               // (kernels already queued may still use the blocks that go back to the cache)
+    GmgBatchBuilder b(sc, s);
     uint64_t *d_idx = nullptr, *d_len = nullptr, *d_off = nullptr;
-    unsigned long long *d_stats = nullptr;
     GMG_HIP(sc.alloc(&d_idx, (n ? n : 1) * 8));
     GMG_HIP(sc.alloc(&d_len, (n + 1) * 8));
     GMG_HIP(sc.alloc(&d_off, (n + 1) * 8));
-    GMG_HIP(sc.alloc(&d_stats, 8 * sizeof(unsigned long long)));
-    const unsigned long long stats0[6] = {~0ull, 0, 0, 0, ~0ull, 0};
-    unsigned long long stats[6];
-    GMG_HIP(hipMemcpyAsync(d_stats, stats0, sizeof stats0, hipMemcpyHostToDevice, s));
+    { const int rc = b.begin(); if (rc) return rc; }
     if (n) GMG_HIP(hipMemcpyAsync(d_idx, idx, n * 8, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_sel_len, dim3((unsigned)((n + 256) / 256 < 512 ? (n + 256) / 256 : 512)), dim3(256), 0, s, reads->d_off, d_idx, n, reads->n_reads, d_len, d_stats);
+    hipLaunchKernelGGL(k_sel_len, dim3(gmg_grid(n + 1, 256, 512)), dim3(256), 0, s, reads->d_off, d_idx, n, reads->n_reads, d_len, b.d_stats);
     GMG_HIP((gmg_scan_excl<uint64_t, uint64_t>(d_len, d_off, n + 1, s)));
-    GMG_HIP(hipMemcpyAsync(&stats[5], d_off + n, 8, hipMemcpyDeviceToHost, s));
-    GMG_HIP(hipMemcpyAsync(stats, d_stats, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    GMG_HIP(hipStreamSynchronize(s));
-    if (stats[4] != ~0ull)
-        return gmg_set_error(GMG_ERANGE, "gmg_reads_select: entry %llu names a read beyond the batch's %llu", stats[4], (unsigned long long)reads->n_reads);
-    // the packed words (guards zeroed; the gather writes every data word), the tile table, the gather
-    const uint64_t total = stats[5], data_words = (total + 15) / 16;
-    uint32_t *alloc = nullptr;
-    GMG_HIP(sc.alloc(&alloc, (data_words + 2 * GMG_GUARD_WORDS) * 4));
-    GMG_HIP(hipMemsetAsync(alloc, 0, GMG_GUARD_WORDS * 4, s));
-    GMG_HIP(hipMemsetAsync(alloc + GMG_GUARD_WORDS + data_words, 0, GMG_GUARD_WORDS * 4, s));
-    gmg_reads tmp;                                      // (the batch goes to the heap once nothing can fail any more)
-    memset(&tmp, 0, sizeof tmp);
-    tmp.n_reads = n;
-    tmp.total_bases = total;
-    tmp.d_off = d_off;
-    tmp.owns_off = 1;
-    tmp.n_words = data_words + GMG_GUARD_WORDS;
-    tmp.d_packed_alloc = alloc;
-    tmp.d_packed = alloc + GMG_GUARD_WORDS;
-    { const int rc = gmg_reads_tile_table(&tmp, sc, s); if (rc) return rc; }
-    if (data_words) {
-        const uint64_t blocks = (tmp.n_tiles + 3) / 4;     // one wave per tile
-        hipLaunchKernelGGL(k_reads_select, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, reads->d_packed, reads->d_off, d_idx,
-                           d_off, tmp.d_tile_read, n, total, alloc + GMG_GUARD_WORDS);
-        GMG_HIP(hipGetLastError());
-    }
-    GMG_HIP(hipStreamSynchronize(s));
-    gmg_reads_set_lengths(&tmp, stats);
-    gmg_reads *r = new (std::nothrow) gmg_reads(tmp);
-    if (!r) return gmg_set_error(GMG_ENOMEM, "gmg_reads_select: out of host memory");
-    sc.detach(d_off); sc.detach(alloc); sc.detach(tmp.d_tile_read);
-    sc.wait = GmgScratch::NONE;                         // (waited for just now)
-    *out = r;
-    return GMG_OK;
+    { const int rc = b.lengths(d_off + n); if (rc) return rc; }
+    if (b.stats[4] != ~0ull)
+        return gmg_set_error(GMG_ERANGE, "gmg_reads_select: entry %llu names a read beyond the batch's %llu", b.stats[4], (unsigned long long)reads->n_reads);
+    { const int rc = b.layout(n, d_off); if (rc) return rc; }
+    if (b.data_words)
+        hipLaunchKernelGGL(k_reads_select, dim3(b.gather_grid()), dim3(256), 0, s, reads->d_packed, reads->d_off, d_idx, d_off, b.tmp.d_tile_read, n,
+                           b.total, b.d_words);
+    return b.finish("gmg_reads_select", out);
 }
 
 extern "C" int gmg_reads_free(gmg_reads *r)

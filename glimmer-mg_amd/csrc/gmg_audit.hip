@@ -28,6 +28,7 @@
 
 #define AU_BLOCK 256             // four waves, a region each
 #define AU_WAVES (AU_BLOCK / 64)
+#define AU_GRID_CAP (256 * 32)   // 8 work-groups of four waves per CU, 4 rounds; the rest loops
 #define AU_BINS 65               // the 64 codons, then the regions without a first codon
 
 struct AuditArgs {
@@ -46,59 +47,24 @@ struct gmg_audit {
 
 // stats of a call: [0] first bad region
 struct AuRegion {
-    const uint32_t *packed;
+    DevRegion v;
     const uint64_t *amb;
-    uint64_t base, amb_lo, amb_hi;       // the read's base 0; its part of the list
-    int64_t n, first;                    // the read's length, the region's base 0
-    bool fwd;
+    uint64_t amb_lo, amb_hi;             // the read's part of the list
 };
-
-// the first index i in [0, n) with a[i] >= key (n: none), a ascending; every lane gets the answer.  64 probes a round.
-__device__ __forceinline__ uint64_t au_wave_lower_bound(const uint64_t *__restrict__ a, uint64_t n, uint64_t key, int lane)
-{
-    uint64_t lo = 0, hi = n;                                            // the answer lies in [lo, hi]
-    while (hi > lo) {
-        const uint64_t step = (hi - lo + 63) / 64, idx = lo + step * (uint64_t)lane;
-        const bool less = idx < hi && a[idx] < key;                     // true on a prefix of the lanes
-        const int k = __popcll(__ballot(less));
-        if (k == 0) hi = lo;
-        else {
-            const uint64_t top = lo + step * (uint64_t)k;
-            lo = lo + step * (uint64_t)(k - 1) + 1;
-            hi = top < hi ? top : hi;
-        }
-    }
-    return lo;
-}
 
 __device__ __forceinline__ bool au_listed(const uint64_t *__restrict__ amb, uint64_t lo, uint64_t hi, uint64_t g)
 {
-    uint64_t l = lo, h = hi;
-    while (l < h) {
-        const uint64_t m = (l + h) >> 1;
-        if (amb[m] < g) l = m + 1;
-        else h = m;
-    }
+    const uint64_t l = dev_lower_bound(amb, lo, hi, g);
     return l < hi && amb[l] == g;
 }
 
 // codon index of region offsets r, r + 1, r + 2 (0 <= r < n; the three bases wrap one by one), -1 with a listed base
 __device__ __forceinline__ int au_codon(const AuRegion &R, int64_t r)
 {
-    int64_t p = R.fwd ? R.first + r : R.first - r;
-    if (p >= R.n) p -= R.n;
-    if (p < 0) p += R.n;
-    int idx = 0;
     bool listed = false;
-#pragma unroll
-    for (int t = 0; t < 3; t++) {
-        const uint64_t g = R.base + (uint64_t)p;
-        const int code = dev_code(R.packed, g);
-        idx = 4 * idx + (R.fwd ? code : 3 - code);
+    const int idx = R.v.codon(r, [&](uint64_t g) {
         if (R.amb_hi > R.amb_lo) listed |= au_listed(R.amb, R.amb_lo, R.amb_hi, g);
-        if (R.fwd) { if (++p >= R.n) p = 0; }
-        else { if (--p < 0) p = R.n - 1; }
-    }
+    });
     return listed ? -1 : idx;
 }
 
@@ -106,19 +72,18 @@ __device__ __forceinline__ int au_codon(const AuRegion &R, int64_t r)
 __device__ __forceinline__ bool au_region(const gmg_gene_region &r, const uint32_t *packed, const uint64_t *__restrict__ off, uint64_t n_reads,
                                           const uint64_t *__restrict__ amb, uint64_t n_amb, int lane, AuRegion &R)
 {
-    if (!(r.read < n_reads && r.strand != 0 && r.first >= 0 && r.len >= 0)) return false;
-    const uint64_t base = off[r.read], L = off[(uint64_t)r.read + 1] - base;
-    if (!((uint64_t)r.first < L && (uint64_t)r.len <= L && L < 0x80000000ull)) return false;
-    R.packed = packed;
+    uint64_t base, L;
+    if (!(dev_region_fits(r, off, n_reads, base, L) && L < 0x80000000ull)) return false;
+    R.v.packed = packed;
+    R.v.base = base;
+    R.v.n = (int64_t)L;
+    R.v.first = r.first;
+    R.v.fwd = r.strand > 0;
     R.amb = amb;
-    R.base = base;
-    R.n = (int64_t)L;
-    R.first = r.first;
-    R.fwd = r.strand > 0;
     R.amb_lo = R.amb_hi = 0;
     if (n_amb) {
-        R.amb_lo = au_wave_lower_bound(amb, n_amb, base, lane);
-        R.amb_hi = au_wave_lower_bound(amb, n_amb, base + L, lane);
+        R.amb_lo = dev_wave_lower_bound(amb, n_amb, base, lane);
+        R.amb_hi = dev_wave_lower_bound(amb, n_amb, base + L, lane);
     }
     return true;
 }
@@ -192,10 +157,10 @@ __global__ __launch_bounds__(AU_BLOCK) void k_audit_count(AuditArgs a, const uin
         // a gene that ends in no stop codon: on round the read, up to the first step with a hit (anomaly.cc:157-176)
         int64_t next = -1;
         if (a.next_stop && stop_which < 0) {
-            for (int64_t j0 = len; j0 < R.n; j0 += 3 * 64) {
+            for (int64_t j0 = len; j0 < R.v.n; j0 += 3 * 64) {
                 const int64_t j = j0 + 3 * lane;
                 bool hit = false;
-                if (j < R.n) {
+                if (j < R.v.n) {
                     const int code = au_codon(R, j);
                     hit = code >= 0 && ((a.stop_mask >> code) & 1ull);
                 }
@@ -247,13 +212,6 @@ __global__ __launch_bounds__(AU_BLOCK) void k_audit_write(AuditArgs a, const uin
             at += (uint64_t)__popcll(m);
         }
     }
-}
-
-static unsigned au_grid(uint64_t n)
-{
-    const uint64_t g = (n + AU_WAVES - 1) / AU_WAVES;
-    const uint64_t cap = 256 * 32;                                      // 8 work-groups of four waves per CU, 4 rounds; the rest loops
-    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
 }
 
 // codon index of three lower-case letters of acgt, -1 for anything else
@@ -324,7 +282,7 @@ extern "C" int gmg_genes_audit(const gmg_reads *reads, const gmg_gene_region *re
         }
         GMG_HIP(hipMemsetAsync(d_stats, 0xff, 8, s));
         GMG_HIP(hipMemcpyAsync(d_regions, regions, n * sizeof(gmg_gene_region), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_audit_count, dim3(au_grid(n)), dim3(AU_BLOCK), 0, s, a, reads->d_packed, reads->d_off, reads->n_reads, d_regions, n,
+        hipLaunchKernelGGL(k_audit_count, dim3(gmg_grid(n, AU_WAVES, AU_GRID_CAP)), dim3(AU_BLOCK), 0, s, a, reads->d_packed, reads->d_off, reads->n_reads, d_regions, n,
                            d_amb, n_amb, d_rec, d_cnt, d_hist, d_stats);
         GMG_HIP(hipGetLastError());
         GMG_HIP((gmg_scan_excl<uint32_t, uint64_t>(d_cnt, d_off, n + 1, s)));
@@ -342,7 +300,7 @@ extern "C" int gmg_genes_audit(const gmg_reads *reads, const gmg_gene_region *re
                                  (unsigned long long)total, gmg_opt(GMG_OPT_MG_MAX_ENTRIES));
         if (total) {
             GMG_HIP(sc.alloc(&d_inner, total * 4));
-            hipLaunchKernelGGL(k_audit_write, dim3(au_grid(n)), dim3(AU_BLOCK), 0, s, a, reads->d_packed, reads->d_off, reads->n_reads, d_regions, n,
+            hipLaunchKernelGGL(k_audit_write, dim3(gmg_grid(n, AU_WAVES, AU_GRID_CAP)), dim3(AU_BLOCK), 0, s, a, reads->d_packed, reads->d_off, reads->n_reads, d_regions, n,
                                d_amb, n_amb, d_rec, d_off, total, d_inner);
             GMG_HIP(hipGetLastError());
         }

@@ -19,6 +19,76 @@ __device__ __forceinline__ int dev_code(const uint32_t *__restrict__ packed, uin
     return (int)((packed[g >> 4] >> (2 * (unsigned)(g & 15))) & 3u);
 }
 
+// the first index i in [lo, hi) with a[i] >= key (hi: none), a ascending
+__device__ __forceinline__ uint64_t dev_lower_bound(const uint64_t *__restrict__ a, uint64_t lo, uint64_t hi, uint64_t key)
+{
+    while (lo < hi) {
+        const uint64_t m = (lo + hi) >> 1;
+        if (a[m] < key) lo = m + 1;
+        else hi = m;
+    }
+    return lo;
+}
+
+// the first index i in [0, n) with a[i] >= key (n: none), a ascending; every lane of the wave gets the answer.  64 probes a round.
+__device__ __forceinline__ uint64_t dev_wave_lower_bound(const uint64_t *__restrict__ a, uint64_t n, uint64_t key, int lane)
+{
+    uint64_t lo = 0, hi = n;                                            // the answer lies in [lo, hi]
+    while (hi > lo) {
+        const uint64_t step = (hi - lo + 63) / 64, idx = lo + step * (uint64_t)lane;
+        const bool less = idx < hi && a[idx] < key;                     // true on a prefix of the lanes
+        const int k = __popcll(__ballot(less));
+        if (k == 0) hi = lo;
+        else {
+            const uint64_t top = lo + step * (uint64_t)k;
+            lo = lo + step * (uint64_t)(k - 1) + 1;
+            hi = top < hi ? top : hi;
+        }
+    }
+    return lo;
+}
+
+// Does a region (include/gmg.h) fit the batch: a read of the batch, a strand, its base 0 inside the read, no longer than the read
+// -> the read's base 0 and its length.  false: nothing of the region may be read.
+__device__ __forceinline__ bool dev_region_fits(const gmg_gene_region &r, const uint64_t *__restrict__ off, uint64_t n_reads, uint64_t &base,
+                                                uint64_t &L)
+{
+    if (!(r.read < n_reads && r.strand != 0 && r.first >= 0 && r.len >= 0)) return false;
+    base = off[r.read];
+    L = off[(uint64_t)r.read + 1] - base;
+    return (uint64_t)r.first < L && (uint64_t)r.len <= L;
+}
+
+// A region as its codons see it: offset i of the region sits at position first + i (forward) or first - i (reverse, read
+// downwards and complemented) of its read, modulo the read's length n (0 < n < 2^31, 0 <= first < n).
+struct DevRegion {
+    const uint32_t *packed;
+    uint64_t base;                       // job-wide index of the read's base 0
+    int64_t n, first;
+    bool fwd;
+    // codon index 16*b0 + 4*b1 + b2 of offsets r, r + 1, r + 2 (0 <= r < n; the three bases wrap one by one); each_base (g) sees
+    // the job-wide index of every one of the three
+    template <class F>
+    __device__ __forceinline__ int codon(int64_t r, F each_base) const
+    {
+        int64_t p = fwd ? first + r : first - r;
+        if (p >= n) p -= n;
+        if (p < 0) p += n;
+        int idx = 0;
+#pragma unroll
+        for (int t = 0; t < 3; t++) {
+            const uint64_t g = base + (uint64_t)p;
+            const int code = dev_code(packed, g);
+            idx = 4 * idx + (fwd ? code : 3 - code);
+            each_base(g);
+            if (fwd) { if (++p >= n) p = 0; }
+            else { if (--p < 0) p = n - 1; }
+        }
+        return idx;
+    }
+    __device__ __forceinline__ int codon(int64_t r) const { return codon(r, [](uint64_t) {}); }
+};
+
 // A scoring buffer B cut from a read (gmg_orient in include/gmg.h).
 struct DevBuf {
     const uint32_t *packed;

@@ -23,17 +23,8 @@
 
 #define EN_BLOCK 256             // four waves, a region each
 #define EN_WAVES (EN_BLOCK / 64)
+#define EN_GRID_CAP (256 * 32)   // 8 work-groups of four waves per CU, 4 rounds; the rest loops
 #define EN_NONE 20               // class of a codon that counts nowhere
-
-// The leading fields of gmg_mg.hip's result handle, as that file defines it (the handle is opaque outside the library; this view
-// is checked against gmg_mg_result_info before it is used).
-struct gmg_mg_result {
-    gmg_mg_orf *d_orfs;
-    gmg_start *d_starts;
-    gmg_start_errors *d_errs;
-    uint64_t *d_read_orf_off;
-    uint64_t n_reads, n_orfs, n_starts;
-};
 
 struct EntropyArgs {
     double pos[20], neg[20];
@@ -88,7 +79,7 @@ __global__ __launch_bounds__(EN_BLOCK) void k_entropy(EntropyArgs a, const uint3
             strand = r.strand;
         }
         const int64_t n_codons = len / 3;                               // a trailing partial codon counts nowhere
-        const bool fwd = strand > 0;
+        const DevRegion R = {packed, base, n, first, strand > 0};
         int cnt[20];
 #pragma unroll
         for (int j = 0; j < 20; j++) cnt[j] = 0;
@@ -100,18 +91,7 @@ __global__ __launch_bounds__(EN_BLOCK) void k_entropy(EntropyArgs a, const uint3
                 // (reads hold fewer than 2^31 bases and len is an int32: 32-bit arithmetic; len <= n needs no division at all)
                 uint32_t r = (uint32_t)(3 * c);
                 if (r >= (uint32_t)n) r %= (uint32_t)n;
-                int64_t p = fwd ? first + r : first - r;
-                if (p >= n) p -= n;
-                if (p < 0) p += n;
-                int idx = 0;
-#pragma unroll
-                for (int t = 0; t < 3; t++) {
-                    const int code = dev_code(packed, base + (uint64_t)p);
-                    idx = 4 * idx + (fwd ? code : 3 - code);
-                    if (fwd) { if (++p >= n) p = 0; }
-                    else { if (--p < 0) p = n - 1; }
-                }
-                cl = s_cls[idx];
+                cl = s_cls[R.codon((int64_t)r)];
             }
 #pragma unroll
             for (int j = 0; j < 20; j++) cnt[j] += __popcll(__ballot(cl == j));
@@ -147,13 +127,6 @@ __global__ __launch_bounds__(EN_BLOCK) void k_entropy(EntropyArgs a, const uint3
         const double ratio = neg_dist == 0.0 ? (pos_dist == 0.0 ? 1.0 : 1e3) : pos_dist / neg_dist;
         if (lane < 3) dist[k * 3 + lane] = lane == 0 ? pos_dist : lane == 1 ? neg_dist : ratio;
     }
-}
-
-static unsigned en_grid(uint64_t n)
-{
-    const uint64_t g = (n + EN_WAVES - 1) / EN_WAVES;
-    const uint64_t cap = 256 * 32;                                      // 8 work-groups of four waves per CU, 4 rounds; the rest loops
-    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
 }
 
 static int en_args(const char *who, const char aa[64], const double pos[20], const double neg[20], EntropyArgs *a)
@@ -200,7 +173,7 @@ extern "C" int gmg_entropy_regions(const gmg_reads *reads, const gmg_gene_region
     if (sc.alloc(&d_regions, n * sizeof(gmg_gene_region)) != hipSuccess)
         return gmg_set_error(GMG_ENOMEM, "gmg_entropy_regions: no device memory for %llu regions", (unsigned long long)n);
     GMG_HIP(hipMemcpyAsync(d_regions, regions, n * sizeof(gmg_gene_region), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_entropy<false>, dim3(en_grid(n)), dim3(EN_BLOCK), 0, s, a, reads->d_packed, reads->d_off, d_regions,
+    hipLaunchKernelGGL(k_entropy<false>, dim3(gmg_grid(n, EN_WAVES, EN_GRID_CAP)), dim3(EN_BLOCK), 0, s, a, reads->d_packed, reads->d_off, d_regions,
                        (const gmg_mg_orf *)nullptr, n, d_counts, d_dist);
     GMG_HIP(hipGetLastError());
     return GMG_OK;
@@ -222,7 +195,7 @@ extern "C" int gmg_entropy_orfs(const gmg_reads *reads, const gmg_mg_result *orf
         return gmg_set_error(GMG_EINVAL, "gmg_entropy_orfs: the result holds %llu ORFs of %llu reads, the batch has %llu reads",
                              (unsigned long long)n, (unsigned long long)orfs->n_reads, (unsigned long long)reads->n_reads);
     if (n == 0 || (!d_counts && !d_dist)) return GMG_OK;
-    hipLaunchKernelGGL(k_entropy<true>, dim3(en_grid(n)), dim3(EN_BLOCK), 0, (hipStream_t)stream, a, reads->d_packed, reads->d_off,
+    hipLaunchKernelGGL(k_entropy<true>, dim3(gmg_grid(n, EN_WAVES, EN_GRID_CAP)), dim3(EN_BLOCK), 0, (hipStream_t)stream, a, reads->d_packed, reads->d_off,
                        (const gmg_gene_region *)nullptr, orfs->d_orfs, n, d_counts, d_dist);
     GMG_HIP(hipGetLastError());
     return GMG_OK;

@@ -119,17 +119,11 @@ __global__ __launch_bounds__(FL_LANE_BLOCK) void k_fixed_lane(FixedArgs a, const
     }
 }
 
-static unsigned fl_grid(uint64_t n, unsigned block, unsigned cap)
-{
-    const uint64_t g = (n + block - 1) / block;
-    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
-}
-
 int gmg_launch_fixed(const gmg_fixed_model *m, const gmg_reads *r, const gmg_segments *sg, int lo, int hi, double *d_out,
                      hipStream_t s)
 {
     // 46 KB of LDS per work-group: three per CU; a grid of three per CU for all 256 CUs stays resident and loads its tables once
-    hipLaunchKernelGGL(k_fixed_lane, dim3(fl_grid(sg->n, FL_LANE_BLOCK, 3 * 256)), dim3(FL_LANE_BLOCK), 0, s, m->a, m->d_mip, m->d_prob,
+    hipLaunchKernelGGL(k_fixed_lane, dim3(gmg_grid(sg->n, FL_LANE_BLOCK, 3 * 256)), dim3(FL_LANE_BLOCK), 0, s, m->a, m->d_mip, m->d_prob,
                        r->d_packed, r->d_off, sg->d_segs, sg->n, lo, hi, d_out);
     GMG_HIP(hipGetLastError());
     return GMG_OK;

@@ -24,6 +24,7 @@
 // Limits: < 2^31 bytes per call, < 2^28 reads, < 2^36 bases.
 
 #include "gmg_device.h"
+#include "gmg_gather.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -423,24 +424,9 @@ __global__ __launch_bounds__(256) void k_fa_hdr_fix(const uint8_t *bytes, uint64
 // shortest / longest read and the reads over 512 bases (what gmg_reads keeps about a batch), from the offsets: stats[0] min, [1] max, [2] count
 __global__ __launch_bounds__(256) void k_fa_stats(const uint64_t *off, uint64_t n_reads, unsigned long long *stats)
 {
-    unsigned long long mn = ~0ull, mx = 0, over = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_reads; i += (uint64_t)gridDim.x * blockDim.x) {
-        const unsigned long long l = off[i + 1] - off[i];
-        mn = l < mn ? l : mn;
-        mx = l > mx ? l : mx;
-        over += l > 512;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long a = __shfl_xor(mn, o), b = __shfl_xor(mx, o);
-        mn = a < mn ? a : mn;
-        mx = b > mx ? b : mx;
-        over += __shfl_xor(over, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (mn != ~0ull) atomicMin(&stats[0], mn);
-        if (mx) atomicMax(&stats[1], mx);
-        if (over) atomicAdd(&stats[2], over);
-    }
+    GmgLenStats st;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_reads; i += (uint64_t)gridDim.x * blockDim.x) st.length(off[i + 1] - off[i]);
+    st.finish(stats);                                   // (no item is bad: stats[4] is never touched)
 }
 
 // the copy stream of the chunked upload and its events (one set per process: ingest calls of different threads take turns on it)

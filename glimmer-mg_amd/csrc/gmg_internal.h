@@ -76,6 +76,15 @@ struct gmg_reads {
     uint64_t n_over_512;         // reads longer than 512 bases (tile shape of the mg running-sum kernel)
 };
 
+// gmg_mg_score_reads' result handle (gmg_mg.hip; gmg_entropy.hip reads its ORFs)
+struct gmg_mg_result {
+    gmg_mg_orf *d_orfs;
+    gmg_start *d_starts;
+    gmg_start_errors *d_errs;    // error branch only: parallel to d_starts
+    uint64_t *d_read_orf_off;    // [n_reads + 1]
+    uint64_t n_reads, n_orfs, n_starts;
+};
+
 struct gmg_null_set {
     float *d_tab;                // [n][252]: [3][64] full windows, then [3][20] partial windows of each model
     int n;
@@ -155,6 +164,13 @@ enum GmgOpt {
 };
 extern long long g_gmg_opt[GMG_OPT_COUNT];
 static inline long long gmg_opt(int k) { return g_gmg_opt[k]; }
+
+// blocks of a grid-stride kernel that takes per_block items a block: enough for all items, one at least, cap at most (the rest loops)
+static inline unsigned gmg_grid(uint64_t n_items, uint64_t per_block, uint64_t cap)
+{
+    const uint64_t g = (n_items + per_block - 1) / per_block;
+    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
+}
 
 // cache of device blocks for scratch and result buffers (gmg_api.hip): hipMalloc / hipFree of GB-sized buffers cost up
 // to hundreds of milliseconds now and then; a released block is handed to the next request it fits

@@ -38,14 +38,6 @@
 #include <type_traits>
 #include <vector>
 
-struct gmg_mg_result {
-    gmg_mg_orf *d_orfs;
-    gmg_start *d_starts;
-    gmg_start_errors *d_errs;    // error branch only: parallel to d_starts
-    uint64_t *d_read_orf_off;    // [n_reads + 1]
-    uint64_t n_reads, n_orfs, n_starts;
-};
-
 // One Score_Orf_Starts call waiting to be walked, 32 bytes (the count passes write and read 100 M + 77 M of them per 1 M reads
 // with -i: as 56-byte structs with one field per value they were 30 GB of the call's traffic).  Reads of the level kernels are
 // shorter than 2,040 bases, so every position fits 12 bits:

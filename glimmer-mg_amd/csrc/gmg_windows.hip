@@ -32,6 +32,7 @@
 #include <new>
 
 #define WN_BLOCK 256
+#define WN_GRID_CAP (256 * 32)
 
 struct gmg_windows {
     uint64_t *d_off;                     // n_reads + 1
@@ -46,35 +47,6 @@ struct gmg_gaps {
     uint64_t n_reads, n_gaps;
     hipStream_t s;
 };
-
-// the first index i in [0, n) with a[i] >= key (n: none), a ascending; every lane of the wave gets the answer.  64 probes a round.
-__device__ __forceinline__ uint64_t wn_wave_lower_bound(const uint64_t *__restrict__ a, uint64_t n, uint64_t key, int lane)
-{
-    uint64_t lo = 0, hi = n;
-    while (hi > lo) {
-        const uint64_t step = (hi - lo + 63) / 64, idx = lo + step * (uint64_t)lane;
-        const bool less = idx < hi && a[idx] < key;                     // true on a prefix of the lanes
-        const int k = __popcll(__ballot(less));
-        if (k == 0) hi = lo;
-        else {
-            const uint64_t top = lo + step * (uint64_t)k;
-            lo = lo + step * (uint64_t)(k - 1) + 1;
-            hi = top < hi ? top : hi;
-        }
-    }
-    return lo;
-}
-
-// the first index i in [lo, hi) with a[i] >= key (hi: none)
-__device__ __forceinline__ uint64_t wn_lower_bound(const uint64_t *__restrict__ a, uint64_t lo, uint64_t hi, uint64_t key)
-{
-    while (lo < hi) {
-        const uint64_t m = (lo + hi) >> 1;
-        if (a[m] < key) lo = m + 1;
-        else hi = m;
-    }
-    return lo;
-}
 
 // c, g, t among the 2-bit fields of w
 __device__ __forceinline__ void wn_word_counts(uint32_t w, uint32_t &c, uint32_t &g, uint32_t &t)
@@ -171,8 +143,8 @@ __global__ __launch_bounds__(WN_BLOCK) void k_win_rows(WnSums q, const uint64_t 
         __syncthreads();                                                // (the round before has read s_out, s_r, s_amb)
         if (tid < 64) {
             // the read of row x: the last r with row_off[r] <= x = (the first r with row_off[r] >= x + 1) - 1
-            const uint64_t a = wn_wave_lower_bound(row_off, n_reads + 1, j0 + 1, lane) - 1;
-            const uint64_t b = wn_wave_lower_bound(row_off, n_reads + 1, j0 + rows, lane) - 1;
+            const uint64_t a = dev_wave_lower_bound(row_off, n_reads + 1, j0 + 1, lane) - 1;
+            const uint64_t b = dev_wave_lower_bound(row_off, n_reads + 1, j0 + rows, lane) - 1;
             if (lane == 0) { s_r[0] = a; s_r[1] = b; }
         }
         __syncthreads();
@@ -196,13 +168,13 @@ __global__ __launch_bounds__(WN_BLOCK) void k_win_rows(WnSums q, const uint64_t 
         if (n_amb) {                                                    // (the same in every lane of the grid)
             __syncthreads();
             if (tid < 64) {
-                const uint64_t a = wn_wave_lower_bound(amb, n_amb, s_pos[0], lane);
-                const uint64_t b = wn_wave_lower_bound(amb, n_amb, s_pos[1], lane);
+                const uint64_t a = dev_wave_lower_bound(amb, n_amb, s_pos[0], lane);
+                const uint64_t b = dev_wave_lower_bound(amb, n_amb, s_pos[1], lane);
                 if (lane == 0) { s_amb[0] = a; s_amb[1] = b; }
             }
             __syncthreads();
             if (active && s_amb[1] > s_amb[0]) {
-                const uint64_t a = wn_lower_bound(amb, s_amb[0], s_amb[1], s), b = wn_lower_bound(amb, a, s_amb[1], e);
+                const uint64_t a = dev_lower_bound(amb, s_amb[0], s_amb[1], s), b = dev_lower_bound(amb, a, s_amb[1], e);
                 other = (uint32_t)(b - a);
                 if (other) { oc = ac[b] - ac[a]; og = ag[b] - ag[a]; ot = at[b] - at[a]; }
             }
@@ -220,12 +192,6 @@ __global__ __launch_bounds__(WN_BLOCK) void k_win_rows(WnSums q, const uint64_t 
         int32_t *dst = out + j0 * 5;
         for (uint64_t x = (uint64_t)tid; x < rows * 5; x += WN_BLOCK) dst[x] = s_out[x];
     }
-}
-
-static unsigned wn_grid(uint64_t n_items)
-{
-    const uint64_t g = (n_items + WN_BLOCK - 1) / WN_BLOCK, cap = 256 * 32;
-    return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
 }
 
 extern "C" int gmg_window_counts(const gmg_reads *reads, int64_t window_len, int64_t window_skip, const uint64_t *amb_base, uint64_t n_amb,
@@ -250,7 +216,7 @@ extern "C" int gmg_window_counts(const gmg_reads *reads, int64_t window_len, int
     GMG_HIP(sc.alloc(&d_cnt, (n_reads + 1) * 4));
     GMG_HIP(sc.alloc(&d_stats, 8));
     GMG_HIP(hipMemsetAsync(d_stats, 0xff, 8, s));
-    hipLaunchKernelGGL(k_win_reads, dim3(wn_grid(n_reads + 1)), dim3(WN_BLOCK), 0, s, reads->d_off, n_reads, W, S, d_cnt, d_stats);
+    hipLaunchKernelGGL(k_win_reads, dim3(gmg_grid(n_reads + 1, WN_BLOCK, WN_GRID_CAP)), dim3(WN_BLOCK), 0, s, reads->d_off, n_reads, W, S, d_cnt, d_stats);
     GMG_HIP(hipGetLastError());
     GMG_HIP((gmg_scan_excl<uint32_t, uint64_t>(d_cnt, d_row_off, n_reads + 1, s)));
     // the running counts do not depend on the number of windows: queued before the wait
@@ -262,7 +228,7 @@ extern "C" int gmg_window_counts(const gmg_reads *reads, int64_t window_len, int
         GMG_HIP(sc.alloc(&d_b[k], n_blocks * 4));
         GMG_HIP(sc.alloc(&d_p[k], n_blocks * 4));
     }
-    hipLaunchKernelGGL(k_win_blocks, dim3(wn_grid(n_blocks)), dim3(WN_BLOCK), 0, s, reads->d_packed, reads->n_words, n_blocks, d_b[0], d_b[1], d_b[2]);
+    hipLaunchKernelGGL(k_win_blocks, dim3(gmg_grid(n_blocks, WN_BLOCK, WN_GRID_CAP)), dim3(WN_BLOCK), 0, s, reads->d_packed, reads->n_words, n_blocks, d_b[0], d_b[1], d_b[2]);
     GMG_HIP(hipGetLastError());
     for (int k = 0; k < 3; k++) GMG_HIP((gmg_scan_excl<uint32_t, uint32_t>(d_b[k], d_p[k], n_blocks, s)));
     if (n_amb) {
@@ -272,7 +238,7 @@ extern "C" int gmg_window_counts(const gmg_reads *reads, int64_t window_len, int
             GMG_HIP(sc.alloc(&d_f[k], (n_amb + 1) * 4));
             GMG_HIP(sc.alloc(&d_a[k], (n_amb + 1) * 4));
         }
-        hipLaunchKernelGGL(k_win_amb, dim3(wn_grid(n_amb + 1)), dim3(WN_BLOCK), 0, s, reads->d_packed, d_amb, n_amb, d_f[0], d_f[1], d_f[2]);
+        hipLaunchKernelGGL(k_win_amb, dim3(gmg_grid(n_amb + 1, WN_BLOCK, WN_GRID_CAP)), dim3(WN_BLOCK), 0, s, reads->d_packed, d_amb, n_amb, d_f[0], d_f[1], d_f[2]);
         GMG_HIP(hipGetLastError());
         for (int k = 0; k < 3; k++) GMG_HIP((gmg_scan_excl<uint32_t, uint32_t>(d_f[k], d_a[k], n_amb + 1, s)));
     }
@@ -292,7 +258,7 @@ extern "C" int gmg_window_counts(const gmg_reads *reads, int64_t window_len, int
         WnSums q;
         q.packed = reads->d_packed; q.n_words = reads->n_words;
         q.pc = d_p[0]; q.pg = d_p[1]; q.pt = d_p[2];
-        hipLaunchKernelGGL(k_win_rows, dim3(wn_grid(total)), dim3(WN_BLOCK), 0, s, q, reads->d_off, n_reads, (const uint64_t *)d_row_off, total, W, S,
+        hipLaunchKernelGGL(k_win_rows, dim3(gmg_grid(total, WN_BLOCK, WN_GRID_CAP)), dim3(WN_BLOCK), 0, s, q, reads->d_off, n_reads, (const uint64_t *)d_row_off, total, W, S,
                            (const uint64_t *)d_amb, n_amb, (const uint32_t *)d_a[0], (const uint32_t *)d_a[1], (const uint32_t *)d_a[2], d_counts);
         GMG_HIP(hipGetLastError());
     }
@@ -409,7 +375,7 @@ __global__ __launch_bounds__(WN_BLOCK) void k_gap_items(const uint64_t *__restri
             m = x + it.read;
         } else {
             const uint64_t r = x - n;
-            const uint64_t e = wn_lower_bound(key, 0, n, (r + 1) << 32);    // behind read r's last interval
+            const uint64_t e = dev_lower_bound(key, 0, n, (r + 1) << 32);    // behind read r's last interval
             it.read = (uint32_t)r;
             it.a = 0;
             if (e) {
@@ -420,7 +386,7 @@ __global__ __launch_bounds__(WN_BLOCK) void k_gap_items(const uint64_t *__restri
             m = e + r;
             if (WRITE) {
                 // read r's first item: its first interval, or this tail
-                const uint64_t b = wn_lower_bound(key, 0, e, r << 32);
+                const uint64_t b = dev_lower_bound(key, 0, e, r << 32);
                 read_gap_off[r] = slot[b + r];
             }
         }
@@ -458,7 +424,7 @@ extern "C" int gmg_regions_uncovered(const gmg_reads *reads, const gmg_interval 
     GMG_HIP(sc.alloc(&d_slot, (n_items + 1) * 8));
     GMG_HIP(hipMemsetAsync(d_stats, 0xff, 16, s));
     if (n_reads) {
-        hipLaunchKernelGGL(k_gap_reads, dim3(wn_grid(n_reads)), dim3(WN_BLOCK), 0, s, reads->d_off, n_reads, d_stats);
+        hipLaunchKernelGGL(k_gap_reads, dim3(gmg_grid(n_reads, WN_BLOCK, WN_GRID_CAP)), dim3(WN_BLOCK), 0, s, reads->d_off, n_reads, d_stats);
         GMG_HIP(hipGetLastError());
     }
     if (n) {
@@ -469,7 +435,7 @@ extern "C" int gmg_regions_uncovered(const gmg_reads *reads, const gmg_interval 
         GMG_HIP(sc.alloc(&d_val2, n * 8));
         GMG_HIP(sc.alloc(&d_run, n * 8));
         GMG_HIP(hipMemcpyAsync(d_iv, intervals, n * sizeof(gmg_interval), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_gap_keys, dim3(wn_grid(n)), dim3(WN_BLOCK), 0, s, d_iv, n, reads->d_off, n_reads, d_key, d_val, d_stats);
+        hipLaunchKernelGGL(k_gap_keys, dim3(gmg_grid(n, WN_BLOCK, WN_GRID_CAP)), dim3(WN_BLOCK), 0, s, d_iv, n, reads->d_off, n_reads, d_key, d_val, d_stats);
         GMG_HIP(hipGetLastError());
         // (read, lo) ascending: the key bits that can be set are the 31 of lo and those of the read index
         int end_bit = 32;
@@ -496,7 +462,7 @@ extern "C" int gmg_regions_uncovered(const gmg_reads *reads, const gmg_interval 
                              bad[0], v.read, v.lo, v.hi, (unsigned long long)n_reads);
     }
     uint64_t total = 0;
-    hipLaunchKernelGGL(k_gap_items<false>, dim3(wn_grid(n_items + 1)), dim3(WN_BLOCK), 0, s, (const uint64_t *)d_key2, (const uint64_t *)d_run, n,
+    hipLaunchKernelGGL(k_gap_items<false>, dim3(gmg_grid(n_items + 1, WN_BLOCK, WN_GRID_CAP)), dim3(WN_BLOCK), 0, s, (const uint64_t *)d_key2, (const uint64_t *)d_run, n,
                        reads->d_off, n_reads, min_len, d_flag, (const uint64_t *)nullptr, (uint64_t)0, (gmg_gene_region *)nullptr, (uint64_t *)nullptr);
     GMG_HIP(hipGetLastError());
     GMG_HIP((gmg_scan_excl<uint32_t, uint64_t>(d_flag, d_slot, n_items + 1, s)));
@@ -507,7 +473,7 @@ extern "C" int gmg_regions_uncovered(const gmg_reads *reads, const gmg_interval 
                              (unsigned long long)total, gmg_opt(GMG_OPT_MG_MAX_ENTRIES));
     gmg_gene_region *d_gaps = nullptr;
     GMG_HIP(sc.alloc(&d_gaps, (total ? total : 1) * sizeof(gmg_gene_region)));
-    hipLaunchKernelGGL(k_gap_items<true>, dim3(wn_grid(n_items + 1)), dim3(WN_BLOCK), 0, s, (const uint64_t *)d_key2, (const uint64_t *)d_run, n,
+    hipLaunchKernelGGL(k_gap_items<true>, dim3(gmg_grid(n_items + 1, WN_BLOCK, WN_GRID_CAP)), dim3(WN_BLOCK), 0, s, (const uint64_t *)d_key2, (const uint64_t *)d_run, n,
                        reads->d_off, n_reads, min_len, (uint32_t *)nullptr, (const uint64_t *)d_slot, total, d_gaps, d_gap_off);
     GMG_HIP(hipGetLastError());
     gmg_gaps *res = new (std::nothrow) gmg_gaps();
