@@ -568,6 +568,99 @@ def extract_plan(offsets, coords, flags=0, min_len=0):
     return [(r.read, r.first, r.len, r.strand) for r in out[:n.value]], line[:n.value].copy()
 
 
+def text_params(width=60, fwd=None, rev=None):
+    """gmg_text_params_reference (host): the tables extract prints through -- every byte itself on the forward strand, the
+    reference's Complement on the reverse strand -- unless fwd / rev (256 bytes each) replace them"""
+    p = capi.TextParams()
+    _ck(capi.lib().gmg_text_params_reference(C.byref(p), int(width)))
+    for name, tab in (("fwd", fwd), ("rev", rev)):
+        if tab is not None:
+            tab = bytes(tab)
+            assert len(tab) == 256
+            C.memmove(getattr(p, name), tab, 256)
+    return p
+
+
+class Letters:
+    """gmg_letters: the sequence bytes of a batch in HBM, one per base, and the text of regions of them (gmg_regions_text)"""
+
+    def __init__(self, letters, offsets):
+        letters = bytes(letters)
+        self.offsets = np.ascontiguousarray(offsets, np.uint64)
+        assert len(letters) == int(self.offsets[-1])
+        self.h = C.c_void_p()
+        _ck(capi.lib().gmg_letters_upload(letters, _ptr(self.offsets), len(self.offsets) - 1, C.byref(self.h)))
+
+    @staticmethod
+    def _args(regions, heads):
+        """regions [(read, first, len, strand)] or a GeneRegion array; heads: a list of bytes, or (blob, offsets)"""
+        n = len(regions)
+        if not isinstance(regions, C.Array):
+            regions = (capi.GeneRegion * max(n, 1))(*[capi.GeneRegion(*[int(x) for x in r]) for r in regions])
+        if isinstance(heads, tuple):
+            blob, off = bytes(heads[0]), np.ascontiguousarray(heads[1], np.uint64)
+        else:
+            assert len(heads) == n
+            blob = b"".join(heads)
+            off = np.zeros(n + 1, np.uint64)
+            off[1:] = np.cumsum([len(h) for h in heads], dtype=np.uint64)
+        return regions, n, blob, off
+
+    def _size(self, regions, n, blob, off, params):
+        size = C.c_size_t(0)
+        _ck(capi.lib().gmg_regions_text(self.h, regions, n, blob, _ptr(off), C.byref(params), None, C.byref(size), None))
+        return size.value
+
+    def text_size(self, regions, heads, params):
+        """gmg_regions_text with host_out = NULL: the length of the text"""
+        return self._size(*self._args(regions, heads), params)
+
+    def regions_text(self, regions, heads, params, capacity=None, out=None):
+        """gmg_regions_text -> the text (bytes).  capacity: the size of the host buffer (default: what text_size says); out: a
+        uint8 array to write into instead (its size is the capacity), then the length is returned"""
+        regions, n, blob, off = self._args(regions, heads)
+        if out is None:
+            if capacity is None:
+                capacity = self._size(regions, n, blob, off, params)
+            buf = np.zeros(max(int(capacity), 1), np.uint8)
+        else:
+            buf, capacity = out, out.size
+        size = C.c_size_t(int(capacity))
+        _ck(capi.lib().gmg_regions_text(self.h, regions, n, blob, _ptr(off), C.byref(params), _ptr(buf), C.byref(size), None))
+        return size.value if out is not None else buf[:size.value].tobytes()
+
+    def regions_text_device(self, regions, heads, params):
+        """gmg_regions_text_device -> (device pointer, bytes): the text stays in the handle's buffer until the next call"""
+        regions, n, blob, off = self._args(regions, heads)
+        ptr, size = C.c_void_p(), C.c_size_t(0)
+        _ck(capi.lib().gmg_regions_text_device(self.h, regions, n, blob, _ptr(off), C.byref(params), C.byref(ptr), C.byref(size), None))
+        return ptr, size.value
+
+    def kernel_ms(self):
+        ms = C.c_float()
+        _ck(capi.lib().gmg_letters_kernel_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if self.h:
+            capi.lib().gmg_letters_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def memcpy_d2h(ptr, nbytes):
+    """nbytes of device memory at ptr as bytes (gmg_memcpy_d2h)"""
+    out = np.empty(max(int(nbytes), 1), np.uint8)
+    if nbytes:
+        _ck(capi.lib().gmg_memcpy_d2h(_ptr(out), ptr, int(nbytes), None))
+    return out[:int(nbytes)].tobytes()
+
+
 def icm_train_reads(reads, model_len=12, model_depth=7, periodicity=3):
     return Icm.train_reads(reads, model_len, model_depth, periodicity)
 

@@ -6,7 +6,7 @@ import subprocess
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(PKG, "lib", "libgmg.so")
-SOURCES = ["csrc/gmg_api.hip", "csrc/gmg_kernels.hip", "csrc/gmg_frame6.hip", "csrc/gmg_orfs.hip", "csrc/gmg_mg.hip", "csrc/gmg_ingest.hip", "csrc/gmg_strings.hip", "csrc/gmg_train.hip", "csrc/gmg_fixed.hip", "csrc/gmg_tophits.hip", "csrc/gmg_models.hip", "csrc/gmg_entropy.hip", "csrc/gmg_extract.hip", "csrc/gmg_splice.hip", "csrc/gmg_features.hip", "csrc/gmg_audit.hip", "csrc/gmg_windows.hip", "host/icm.cc", "host/icm_train.cc", "host/fixed_icm.cc", "host/gmg_icm_c.cc", "host/gmg_shard.cc", "host/gmg_classes.cc", "host/gmg_extract_plan.cc", "host/gmg_edits_plan.cc", "host/gmg_uncovered_plan.cc", "host/gmg_features_host.cc"]
+SOURCES = ["csrc/gmg_api.hip", "csrc/gmg_kernels.hip", "csrc/gmg_frame6.hip", "csrc/gmg_orfs.hip", "csrc/gmg_mg.hip", "csrc/gmg_ingest.hip", "csrc/gmg_strings.hip", "csrc/gmg_train.hip", "csrc/gmg_fixed.hip", "csrc/gmg_tophits.hip", "csrc/gmg_models.hip", "csrc/gmg_entropy.hip", "csrc/gmg_extract.hip", "csrc/gmg_splice.hip", "csrc/gmg_features.hip", "csrc/gmg_audit.hip", "csrc/gmg_windows.hip", "csrc/gmg_text.hip", "host/icm.cc", "host/icm_train.cc", "host/fixed_icm.cc", "host/gmg_icm_c.cc", "host/gmg_shard.cc", "host/gmg_classes.cc", "host/gmg_extract_plan.cc", "host/gmg_edits_plan.cc", "host/gmg_uncovered_plan.cc", "host/gmg_features_host.cc"]
 HEADERS = ["csrc/gmg_internal.h", "csrc/gmg_device.h", "csrc/gmg_scan.h", "csrc/gmg_gather.h", "csrc/gmg_mg_errtile.h", "csrc/gmg_mg_errwave.h", "csrc/gmg_mg_orfbits.h", "csrc/gmg_mg_run.h", "host/icm.hh", "host/icm_internal.hh", "../include/gmg.h", "../include/gmg_icm.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-Wall", "-Wno-unused-function"]

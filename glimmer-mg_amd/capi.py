@@ -24,6 +24,10 @@ class Coord(C.Structure):
     _fields_ = [("read", C.c_uint32), ("dir", C.c_int32), ("start", C.c_int64), ("end", C.c_int64)]
 
 
+class TextParams(C.Structure):
+    _fields_ = [("fwd", C.c_uint8 * 256), ("rev", C.c_uint8 * 256), ("width", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class SpliceRun(C.Structure):
     _fields_ = [("read", C.c_uint32), ("first", C.c_uint32), ("len", C.c_uint32), ("kind", C.c_uint32)]
 
@@ -116,6 +120,12 @@ PROTOTYPES = {
     "gmg_reads_extract": (i32, [vp, vp, u64, i32, vp, vp, u64, C.POINTER(vp)]),
     "gmg_fasta_ambiguous": (i32, [C.c_char_p, u64, vp, vp, u64, C.POINTER(u64)]),
     "gmg_extract_plan": (i32, [vp, u64, vp, u64, i32, C.c_int64, vp, vp, C.POINTER(u64)]),
+    "gmg_letters_upload": (i32, [vp, vp, u64, C.POINTER(vp)]),
+    "gmg_letters_free": (i32, [vp]),
+    "gmg_letters_kernel_ms": (i32, [vp, C.POINTER(C.c_float)]),
+    "gmg_text_params_reference": (i32, [vp, C.c_uint32]),
+    "gmg_regions_text": (i32, [vp, vp, u64, vp, vp, vp, vp, C.POINTER(C.c_size_t), vp]),
+    "gmg_regions_text_device": (i32, [vp, vp, u64, vp, vp, vp, C.POINTER(vp), C.POINTER(C.c_size_t), vp]),
     "gmg_reads_splice": (i32, [vp, vp, u64, vp, u64, i32, C.POINTER(vp)]),
     "gmg_edits_plan": (i32, [vp, u64, vp, u64, vp, vp, C.c_char_p, u64, vp, u64, C.POINTER(u64), vp, vp]),
     "gmg_single_create": (i32, [C.POINTER(vp)]),

@@ -168,7 +168,8 @@ int gmg_reads_download(const gmg_reads *reads, uint32_t *packed2bit, uint64_t *b
  * null model of their classes (src/Glimmer/glimmer-mg.cc:361-375, 2050-2068) -- one gmg_mg_score_reads call per group. */
 int gmg_reads_select(const gmg_reads *reads, const uint64_t *idx, uint64_t n, gmg_reads **out);
 
-/* ---- regions of reads as a new batch: extract / multi-extract without the text (src/Util/extract.cc, multi-extract.cc) ----
+/* ---- regions of reads as a new batch: what build-icm parses back from the text of extract / multi-extract (src/Util/extract.cc,
+ * multi-extract.cc), without the text in between; the text itself is gmg_regions_text below ----
  * String k of *out is region k (a gmg_gene_region, declared with the entropy calls below, with the meaning they give it): `len`
  * bases of read `read` from the 0-based `first`, read upwards (strand > 0) or downwards and complemented (strand < 0), positions
  * modulo the read's length; empty regions give empty strings.  first in [0, read length), 0 <= len <= read length, strand != 0,
@@ -209,6 +210,43 @@ typedef struct gmg_coord { uint32_t read; int32_t dir; int64_t start, end; } gmg
 #define GMG_COORD_MULTI 16      /* multi-extract's order of the tests */
 int gmg_extract_plan(const uint64_t *base_offsets, uint64_t n_reads, const gmg_coord *coords, uint64_t n, int flags,
                      int64_t min_len, struct gmg_gene_region *regions, uint64_t *coord_of_region, uint64_t *n_regions);
+
+/* ---- regions of reads as text: what extract / multi-extract print (src/Util/extract.cc:158-207, multi-extract.cc:215-262) ----
+ * The reference prints LETTERS, not codes: seq [i] on the forward strand, Complement (seq [i]) on the reverse strand, so the text
+ * is a gather over the sequences' own bytes.  A gmg_letters holds those bytes in HBM, one per base, with the job-wide base
+ * numbering of gmg_fasta_ingest: letters[base_offsets[r] .. base_offsets[r + 1]) is read r (the caller compacts the file on the
+ * host; base_offsets[0] = 0).  The handle also owns the device buffer the text is written to.
+ *
+ * gmg_regions_text: record k of the text is, in order, heads[head_off[k] .. head_off[k + 1]) verbatim (HOST arrays; head_off[0] = 0,
+ * ascending, a head shorter than 2^32 bytes: GMG_EINVAL otherwise), the letters of region k through params->fwd (strand > 0) or
+ * params->rev (strand < 0), with a '\n' in front of a letter whenever params->width letters already stand on the line (width 0:
+ * never), and a final '\n': 61 letters at width 60 give 60 '\n' 1 '\n', 60 letters give 60 '\n', no letter gives '\n'.
+ * A region is a gmg_gene_region with exactly the meaning gmg_reads_extract gives it (positions modulo the read's length, strand < 0
+ * walks downwards), under the same checks -- and a read shorter than 2^31 bases: GMG_ERANGE naming the first bad region
+ * otherwise, with nothing written.  n = 0 is valid and gives 0 bytes.
+ * *bytes: in, the capacity of host_out; out, the length of the text.  host_out NULL only asks for that length (no device
+ * work); a smaller capacity is GMG_ERANGE (*bytes still reports the length, host_out is untouched).  Text offsets are 64-bit.
+ * The text is written by k_regions_text on `stream` and copied to host_out; the call synchronises `stream`.
+ * gmg_regions_text_device: the same text left on the device: *d_text points into a buffer the handle owns, valid until the
+ * next text call on the handle or gmg_letters_free; synchronises `stream` as well.
+ * gmg_letters_kernel_ms: the device time of the last call's write kernel, between two events on its stream (0 when it wrote
+ * nothing).  One call at a time per handle.
+ * gmg_text_params_reference (host only): fwd = every byte itself, rev = the reference's Complement (src/Common/gene.cc:15-19: the
+ * IUPAC pairs in either case, blank * - . _ themselves, any other upper-case letter 'N', everything else 'n'). */
+typedef struct gmg_letters gmg_letters;
+typedef struct gmg_text_params {
+    uint8_t fwd[256], rev[256];  /* the byte printed for a letter on the forward / on the reverse strand */
+    uint32_t width;              /* letters per line; 0 = all on one line */
+    uint32_t reserved;           /* 0 */
+} gmg_text_params;
+int gmg_letters_upload(const char *letters, const uint64_t *base_offsets, uint64_t n_reads, gmg_letters **out);
+int gmg_letters_free(gmg_letters *letters);
+int gmg_letters_kernel_ms(const gmg_letters *letters, float *ms);
+int gmg_text_params_reference(gmg_text_params *params, uint32_t width);
+int gmg_regions_text(gmg_letters *letters, const struct gmg_gene_region *regions, uint64_t n, const char *heads, const uint64_t *head_off,
+                     const gmg_text_params *params, char *host_out, size_t *bytes, void *stream);
+int gmg_regions_text_device(gmg_letters *letters, const struct gmg_gene_region *regions, uint64_t n, const char *heads,
+                            const uint64_t *head_off, const gmg_text_params *params, const char **d_text, size_t *bytes, void *stream);
 
 /* ---- strings spliced from several pieces of a read: scripts/extract_aa.py without the text -------------------------------
  * What glimmer-mg's retraining loop needs under -i / -s: the gene strings with every predicted insertion, deletion and
