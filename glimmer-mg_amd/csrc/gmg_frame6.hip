@@ -22,6 +22,9 @@
 //   k_frame6p   partial-window pass: one lane per (read, buffer position < W-1, strand) recomputes
 //               exactly those bases with the reference's partial-window rule (icm.cc:807-842) and
 //               overwrites them.  2(W-1) of every L bases (4.4 % at L = 500).
+// The modes of k_frame6t and k_frame6p (gene - null table, gene-only rows, groups of reads under their own models, the two strings
+// forms) are launched by the gmg_launch_* functions at the end of this file, all through one main-pass launch (f6_launch_main)
+// and one heads-pass launch (f6_launch_heads).
 // DESIGN.md section 4.1 has the measurements that led here (gathers from L2 -> table swapping).
 
 #include "gmg_device.h"
@@ -44,19 +47,19 @@ extern "C" int gmg_debug_f6_stamps(unsigned long long *out, int n)
 
 struct Frame6Args {
     GmgDevModel gene, nul;
-    const uint32_t *packed;
-    const uint64_t *off;
-    const uint32_t *tile_read;
-    uint64_t total, n_reads;
-    uint64_t first, count;  // k_frame6_generic: range of bases to score
-    uint32_t p_blocks;      // k_frame6p: blocks [0, p_blocks) do partial windows, the rest the tail [first, first+count)
-    double *out;            // [6][stride] gene - null (the Frame_Scores table); stride = total for the public entry point
-    uint64_t stride;        // distance between the rows of `out` in doubles (>= total)
-    float *out_gene;        // gene-only mode (gmg_launch_gene6): [6][gstride] gene values as fp32
-    uint64_t gstride;       // distance between the rows of out_gene in floats (>= total)
+    const uint32_t *packed = nullptr;
+    const uint64_t *off = nullptr;
+    const uint32_t *tile_read = nullptr;
+    uint64_t total = 0, n_reads = 0;
+    uint64_t first = 0, count = 0;  // k_frame6_generic: range of bases to score
+    uint32_t p_blocks = 0;  // k_frame6p: blocks [0, p_blocks) do partial windows, the rest the tail [first, first+count)
+    double *out = nullptr;  // [6][stride] gene - null (the Frame_Scores table); stride = total for the public entry point
+    uint64_t stride = 0;    // distance between the rows of `out` in doubles (>= total)
+    float *out_gene = nullptr;  // gene-only mode (gmg_launch_gene6): [6][gstride] gene values as fp32
+    uint64_t gstride = 0;   // distance between the rows of out_gene in floats (>= total)
     // SUM mode (gmg_launch_strings_sum): per read and string the sum of the values whose window lies inside the read
-    double *str_sums;       // [n_reads][2] (forward string, reverse complement), zeroed by the caller: atomically added to
-    uint32_t uniform_len;   // > 0: every read has this length (read lookups by arithmetic)
+    double *str_sums = nullptr;  // [n_reads][2] (forward string, reverse complement), zeroed by the caller: atomically added to
+    uint32_t uniform_len = 0;    // > 0: every read has this length (read lookups by arithmetic)
     // MULTI mode (gmg_launch_gene6_groups; glimmer-mg -c: consecutive groups of reads, each under its own gene ICM)
     const struct F6Round *rounds = nullptr;     // k_frame6t: runs of <= K whole chunks that lie inside ONE group
     const GmgDevModel *gmodels = nullptr;       // [n_groups] the groups' models (all of one window width)
@@ -781,14 +784,87 @@ __global__ __launch_bounds__(256) void k_frame6_generic(Frame6Args a)
     f6_generic_range(a, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, (uint64_t)gridDim.x * blockDim.x);
 }
 
+// ---------------------------------------------------------------------------
+// Host side.  What the launchers share: the batch's fields of the kernels' argument (f6_args), the main pass's persistent grid
+// (f6_grid) and launch (f6_launch_main), the heads pass (f6_launch_heads) and the any-shape kernel (launch_generic).  What
+// they keep to themselves: which rows they write, what a model off the fast shape means to them, and who scores the batch's tail.
+// ---------------------------------------------------------------------------
+constexpr int F6_BLOCK = 1024, F6_DT = 7;
+constexpr uint32_t F6_SPAN = 2 * F6_BLOCK;              // bases per chunk
+constexpr int F6_K = 16;                                // chunks per round (8 / 12 / 20 measured slower)
+constexpr int F6_K_SUM = 14;                            // ... of the SUM mode: 10 .. 14 take 1.77 - 1.80 ms per model, 16 (128 registers) 1.91, 8 1.84, 24 2.01
+
+// the batch and its gene model; no output rows yet (the gene-only modes never read `nul`)
+static Frame6Args f6_args(const GmgDevModel &gene, const gmg_reads *reads)
+{
+    Frame6Args a;
+    a.gene = gene;
+    a.nul = gene;
+    a.packed = reads->d_packed;
+    a.off = reads->d_off;
+    a.tile_read = reads->d_tile_read;
+    a.total = reads->total_bases;
+    a.n_reads = reads->n_reads;
+    return a;
+}
+
 static int launch_generic(Frame6Args a, uint64_t first, uint64_t count, hipStream_t s)
 {
     if (count == 0) return GMG_OK;
     a.first = first;
     a.count = count;
-    const uint64_t blocks = (count + 255) / 256;
-    const unsigned grid = (unsigned)(blocks < 256 * 16 ? blocks : 256 * 16);
-    hipLaunchKernelGGL(k_frame6_generic, dim3(grid), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_frame6_generic, dim3(gmg_grid(count, 256, 256 * 16)), dim3(256), 0, s, a);
+    GMG_HIP(hipGetLastError());
+    return GMG_OK;
+}
+
+// the main pass's persistent grid: one work-group per CU, shared evenly by the `types` sub-model types that run side by side (3 in the
+// six-frame modes, 1 in the strings modes: all on sub-model 0), no more work-groups of a type than there are units of work
+static int f6_grid(uint64_t units, int types, unsigned *grid)
+{
+    int dev = 0, n_cu = 256;
+    GMG_HIP(hipGetDevice(&dev));
+    GMG_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+    uint64_t nworkers = (uint64_t)(n_cu / types);
+    if (nworkers < 1) nworkers = 1;
+    if (nworkers > units) nworkers = units;
+    *grid = (unsigned)types * (unsigned)nworkers;
+    return GMG_OK;
+}
+
+// The main pass in one of its modes over `units` > 0 chunks (MULTI: rounds).  pair: the rows are 16-byte aligned (even stride), two
+// values per store.  The modes whose callers only ever have such rows (SUM, MULTI, the ablations) are built in that form alone.
+template <int K, int DIAG, bool GENE_ONLY, bool STRINGS = false, bool SUM = false, bool MULTI = false>
+static int f6_launch_main(const Frame6Args &a, uint64_t units, bool pair, hipStream_t s)
+{
+    constexpr bool PAIR_ONLY = SUM || MULTI || DIAG != 0;
+    if (PAIR_ONLY && !pair) return gmg_set_error(GMG_EINVAL, "k_frame6t: this mode needs an even row stride");
+    unsigned grid = 0;
+    { const int rc = f6_grid(units, STRINGS ? 1 : 3, &grid); if (rc) return rc; }
+    const size_t lds = ((size_t)1 << (2 * F6_DT)) * 8;  // dynamic part: half of the leaf values
+    void (*kernel)(Frame6Args) = k_frame6t<F6_BLOCK, F6_DT, K, DIAG, true, GENE_ONLY, STRINGS, SUM, MULTI>;
+    if constexpr (!PAIR_ONLY)
+        if (!pair) kernel = k_frame6t<F6_BLOCK, F6_DT, K, DIAG, false, GENE_ONLY, STRINGS, SUM, MULTI>;
+    GMG_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(F6_BLOCK), lds, s, a);
+    GMG_HIP(hipGetLastError());
+    return GMG_OK;
+}
+
+// The partial-window heads of every read of a batch that has reads (8 reads, 32 lanes each, per block) and, as further blocks of the
+// same launch, the bases the main pass left: the batch tail [first, total) in blocks of 256 bases, or (MULTI) eight blocks per range.
+template <bool GENE, bool MULTI>
+static int f6_launch_heads(Frame6Args a, uint64_t first, hipStream_t s)
+{
+    const unsigned grid = gmg_grid(a.n_reads, 8, 256 * 8);
+    a.first = first;
+    a.count = a.total - first;
+    a.p_blocks = grid;
+    const uint64_t extra = MULTI ? 8ull * a.n_ranges : (a.count + 255) / 256;
+    // (eight blocks per range: with one ICM per read -- up to 2^27 groups -- that would pass the grid limit only at launch time)
+    if (grid + extra > 0x7fffffffull)
+        return gmg_set_error(GMG_ETOOBIG, "gmg_launch_gene6_groups: %llu group edges in one batch: split the batch", (unsigned long long)a.n_ranges);
+    hipLaunchKernelGGL((k_frame6p<7, 4, GENE, MULTI>), dim3(grid + (unsigned)extra), dim3(256), (size_t)3 * a.gene.cstride, s, a);
     GMG_HIP(hipGetLastError());
     return GMG_OK;
 }
@@ -804,74 +880,30 @@ int gmg_launch_frame6(const gmg_model *gene, const gmg_model *nul, const gmg_rea
 int gmg_launch_frame6_strided(const gmg_model *gene, const gmg_model *nul, const gmg_reads *reads, double *d_out,
                               uint64_t stride, hipStream_t s)
 {
-    Frame6Args a;
-    a.gene = gene->dev;
+    Frame6Args a = f6_args(gene->dev, reads);
     a.nul = nul->dev;
-    a.packed = reads->d_packed;
-    a.off = reads->d_off;
-    a.tile_read = reads->d_tile_read;
-    a.total = reads->total_bases;
-    a.n_reads = reads->n_reads;
-    a.first = 0;
-    a.count = 0;
     a.out = d_out;
     a.stride = stride;
-    a.out_gene = nullptr;
-    a.gstride = 0;
-    a.str_sums = nullptr;
-    a.uniform_len = 0;
-    a.str_sums = nullptr;
-    a.uniform_len = 0;
 
-    // the specialised path: completed tree of depth 7 (DEFAULT_MODEL_DEPTH) and the width-3 null model
-    const bool fast = gene->dev.has_fast && gene->dev.D == 7 && nul->dev.has_dense && nul->dev.W == 3 &&
-                      gene->dev.W >= 3 && gene->dev.W <= 15;
-    if (!fast) return launch_generic(a, 0, a.total, s);
+    // the specialised path also wants the width-3 null model; anything else: the whole batch on the any-shape kernel
+    if (!(gmg_f6_shape(gene->dev) && nul->dev.has_dense && nul->dev.W == 3)) return launch_generic(a, 0, a.total, s);
 
-    constexpr int BLOCK = 1024, DT = 7;
-    constexpr uint32_t SPAN = 2 * BLOCK;
-    constexpr int KR = 16;                                         // chunks per round (8 / 12 / 20 measured slower)
-    const uint64_t n_chunks = a.total / SPAN;
+    const uint64_t n_chunks = a.total / F6_SPAN;
     const int diag = (int)gmg_opt(GMG_OPT_DIAG);
-    const bool pair = (a.stride & 1) == 0;          // every row 16-byte aligned
+    const bool pair = (stride & 1) == 0;                // every row 16-byte aligned
     if (n_chunks > 0) {
-        int dev = 0, n_cu = 256;
-        GMG_HIP(hipGetDevice(&dev));
-        GMG_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-        // persistent grid: one work-group per CU, a multiple of the 3 sub-model types
-        unsigned nworkers = (unsigned)(n_cu / 3);
-        if (nworkers < 1) nworkers = 1;
-        if (nworkers > n_chunks) nworkers = (unsigned)n_chunks;
-        const unsigned grid = 3 * nworkers;
-        const size_t lds = ((size_t)1 << (2 * DT)) * 8;            // dynamic part: half of the leaf values
-#define GMG_LAUNCH_F6T(DIAG_, P_)                                                                       \
-    do {                                                                                                \
-        GMG_HIP(hipFuncSetAttribute((const void *)k_frame6t<BLOCK, DT, KR, DIAG_, P_, false>,           \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));             \
-        hipLaunchKernelGGL((k_frame6t<BLOCK, DT, KR, DIAG_, P_, false>), dim3(grid), dim3(BLOCK), lds, s, a); \
-    } while (0)
-        if (diag == 0) { if (pair) GMG_LAUNCH_F6T(0, true); else GMG_LAUNCH_F6T(0, false); }
+        int rc;
+        if (diag == 0) rc = f6_launch_main<F6_K, 0, false>(a, n_chunks, pair, s);
 #ifdef GMG_ABLATIONS
-        else if (diag == 1 && pair) GMG_LAUNCH_F6T(1, true);
-        else if (diag == 2 && pair) GMG_LAUNCH_F6T(2, true);
-        else if (diag == 3 && pair) GMG_LAUNCH_F6T(3, true);
+        else if (diag == 1 && pair) rc = f6_launch_main<F6_K, 1, false>(a, n_chunks, pair, s);
+        else if (diag == 2 && pair) rc = f6_launch_main<F6_K, 2, false>(a, n_chunks, pair, s);
+        else if (diag == 3 && pair) rc = f6_launch_main<F6_K, 3, false>(a, n_chunks, pair, s);
 #endif
         else return gmg_set_error(GMG_EINVAL, "the ablation kernel diag=%d is not in this build", diag);
-#undef GMG_LAUNCH_F6T
-        GMG_HIP(hipGetLastError());
+        if (rc) return rc;
     }
     // partial windows of every read + the last, partial chunk: one launch
-    if (a.n_reads > 0) {
-        const uint64_t blocks = (a.n_reads + 7) / 8;                // 8 reads (32 lanes each) per block
-        const unsigned grid = (unsigned)(blocks < 256 * 8 ? blocks : 256 * 8);
-        const size_t lds_p = (size_t)3 * a.gene.cstride;
-        a.first = n_chunks * SPAN;
-        a.count = a.total - n_chunks * SPAN;
-        a.p_blocks = grid;
-        const unsigned tail_blocks = (unsigned)((a.count + 255) / 256);
-        hipLaunchKernelGGL((k_frame6p<7, 4>), dim3(grid + tail_blocks), dim3(256), lds_p, s, a);
-        GMG_HIP(hipGetLastError());
-    }
+    if (a.n_reads > 0) return f6_launch_heads<false, false>(a, n_chunks * F6_SPAN, s);
     return GMG_OK;
 }
 
@@ -882,60 +914,18 @@ int gmg_launch_frame6_strided(const gmg_model *gene, const gmg_model *nul, const
 // Returns GMG_EBADMODEL when the model shape has no fast path (the caller then takes its exact path).
 static int gene6_impl(const gmg_model *gene, const gmg_reads *reads, float *d_gene, uint64_t gstride, bool full, hipStream_t s)
 {
-    if (!(gene->dev.has_fast && gene->dev.D == 7 && gene->dev.W >= 3 && gene->dev.W <= 15 && gene->dev.P >= 3))
-        return GMG_EBADMODEL;
-    Frame6Args a;
-    a.gene = gene->dev;
-    a.nul = gene->dev;                                 // not used in gene-only mode
-    a.packed = reads->d_packed;
-    a.off = reads->d_off;
-    a.tile_read = reads->d_tile_read;
-    a.total = reads->total_bases;
-    a.n_reads = reads->n_reads;
-    a.first = 0;
-    a.count = 0;
-    a.out = nullptr;
-    a.stride = 0;
+    if (!(gmg_f6_shape(gene->dev) && gene->dev.P >= 3)) return GMG_EBADMODEL;
+    Frame6Args a = f6_args(gene->dev, reads);
     a.out_gene = d_gene;
     a.gstride = gstride;
-    a.str_sums = nullptr;
-    a.uniform_len = 0;
-    constexpr int BLOCK = 1024, DT = 7, KR = 16;
-    constexpr uint32_t SPAN = 2 * BLOCK;
-    const uint64_t n_chunks = a.total / SPAN;
+    const uint64_t n_chunks = a.total / F6_SPAN;
     if (n_chunks > 0) {
-        int dev = 0, n_cu = 256;
-        GMG_HIP(hipGetDevice(&dev));
-        GMG_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-        unsigned nworkers = (unsigned)(n_cu / 3);
-        if (nworkers < 1) nworkers = 1;
-        if (nworkers > n_chunks) nworkers = (unsigned)n_chunks;
-        const unsigned grid = 3 * nworkers;
-        const size_t lds = ((size_t)1 << (2 * DT)) * 8;
-        if ((gstride & 1) == 0) {
-            GMG_HIP(hipFuncSetAttribute((const void *)k_frame6t<BLOCK, DT, KR, 0, true, true>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_frame6t<BLOCK, DT, KR, 0, true, true>), dim3(grid), dim3(BLOCK), lds, s, a);
-        } else {
-            GMG_HIP(hipFuncSetAttribute((const void *)k_frame6t<BLOCK, DT, KR, 0, false, true>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_frame6t<BLOCK, DT, KR, 0, false, true>), dim3(grid), dim3(BLOCK), lds, s, a);
-        }
-        GMG_HIP(hipGetLastError());
+        const int rc = f6_launch_main<F6_K, 0, true>(a, n_chunks, (gstride & 1) == 0, s);
+        if (rc) return rc;
     }
-    if (!full) return launch_generic(a, n_chunks * SPAN, a.total - n_chunks * SPAN, s);
-    // the partial-window heads of every read and the batch tail, as in gmg_launch_frame6_strided
-    if (a.n_reads > 0) {
-        const uint64_t blocks = (a.n_reads + 7) / 8;
-        const unsigned grid = (unsigned)(blocks < 256 * 8 ? blocks : 256 * 8);
-        const size_t lds_p = (size_t)3 * a.gene.cstride;
-        a.first = n_chunks * SPAN;
-        a.count = a.total - n_chunks * SPAN;
-        a.p_blocks = grid;
-        const unsigned tail_blocks = (unsigned)((a.count + 255) / 256);
-        hipLaunchKernelGGL((k_frame6p<7, 4, true>), dim3(grid + tail_blocks), dim3(256), lds_p, s, a);
-        GMG_HIP(hipGetLastError());
-    }
+    if (!full) return launch_generic(a, n_chunks * F6_SPAN, a.total - n_chunks * F6_SPAN, s);
+    // the partial-window heads of every read and the batch tail
+    if (a.n_reads > 0) return f6_launch_heads<true, false>(a, n_chunks * F6_SPAN, s);
     return GMG_OK;
 }
 
@@ -962,18 +952,18 @@ __global__ void k_f6_gather_u64(const uint64_t *src, const uint64_t *idx, uint32
 // list of rounds (runs of <= 16 whole chunks inside one group) and swaps the model in LDS when a work-group crosses into another
 // group, the partial-window pass takes its reads group by group, and the bases no round covers (the chunks that hold a group
 // boundary, the batch tail) go to the exact any-shape code, all in two launches.  Models without the fast path (or of different
-// window widths) make the whole batch take the any-shape kernel, group by group: same values.
+// window widths) make the whole batch take the any-shape kernel, group by group: same values.  The rows are 16-byte aligned
+// (gstride even: every caller pads it to 16 floats or more), the main pass is built for such rows only.
 int gmg_launch_gene6_groups(const gmg_model *const *models, const uint64_t *group_read, int n_groups, const gmg_reads *reads,
                             float *d_gene, uint64_t gstride, hipStream_t s)
 {
     if (!models || !group_read || n_groups < 1 || n_groups > F6_MAX_GROUPS || group_read[0] != 0 || group_read[n_groups] != reads->n_reads)
         return gmg_set_error(GMG_EINVAL, "gmg_launch_gene6_groups: bad group list");
+    if (gstride & 1) return gmg_set_error(GMG_EINVAL, "gmg_launch_gene6_groups: odd row stride %llu", (unsigned long long)gstride);
     for (int g = 0; g < n_groups; g++)
         if (!models[g] || group_read[g + 1] < group_read[g] || models[g]->dev.P < 3)
             return gmg_set_error(GMG_EINVAL, "gmg_launch_gene6_groups: group %d has no periodicity-3 model or an inverted read range", g);
     if (reads->total_bases == 0) return GMG_OK;
-    constexpr int BLOCK = 1024, DT = 7, KR = 16;
-    constexpr uint32_t SPAN = 2 * BLOCK;
 
     // the groups' first bases
     GmgScratch sc(GmgScratch::STREAM, s);
@@ -991,28 +981,14 @@ int gmg_launch_gene6_groups(const gmg_model *const *models, const uint64_t *grou
     }
     sc.wait = GmgScratch::AFTER;                        // nothing below waits: what is still out goes back behind the stream
 
-    Frame6Args a;
-    a.gene = models[0]->dev;
-    a.nul = models[0]->dev;                            // not used in gene-only mode
-    a.packed = reads->d_packed;
-    a.off = reads->d_off;
-    a.tile_read = reads->d_tile_read;
-    a.total = reads->total_bases;
-    a.n_reads = reads->n_reads;
-    a.first = 0;
-    a.count = 0;
-    a.p_blocks = 0;
-    a.out = nullptr;
-    a.stride = 0;
+    Frame6Args a = f6_args(models[0]->dev, reads);
     a.out_gene = d_gene;
     a.gstride = gstride;
-    a.str_sums = nullptr;
-    a.uniform_len = 0;
 
     bool fast = true;
     for (int g = 0; g < n_groups && fast; g++) {
         const GmgDevModel &m = models[g]->dev;
-        fast = m.has_fast && m.D == 7 && m.W >= 3 && m.W <= 15 && m.W == models[0]->dev.W && m.cstride == models[0]->dev.cstride;
+        fast = gmg_f6_shape(m) && m.W == models[0]->dev.W && m.cstride == models[0]->dev.cstride;
     }
     if (!fast) {                                       // any shapes: the exact kernel, group by group
         for (int g = 0; g < n_groups; g++) {
@@ -1028,8 +1004,8 @@ int gmg_launch_gene6_groups(const gmg_model *const *models, const uint64_t *grou
     std::vector<F6Range> ranges;
     std::vector<GmgDevModel> gm(n_groups);
     auto add_range = [&](uint64_t first, uint64_t end, int g) {
-        for (; first < end; first += 4 * SPAN) {        // pieces of at most four chunks: eight blocks each
-            const uint64_t n = end - first < 4 * SPAN ? end - first : 4 * SPAN;
+        for (; first < end; first += 4 * F6_SPAN) {     // pieces of at most four chunks: eight blocks each
+            const uint64_t n = end - first < 4 * F6_SPAN ? end - first : 4 * F6_SPAN;
             ranges.push_back(F6Range{first, (uint32_t)n, (uint32_t)g});
         }
     };
@@ -1037,13 +1013,13 @@ int gmg_launch_gene6_groups(const gmg_model *const *models, const uint64_t *grou
         gm[g] = models[g]->dev;
         const uint64_t b0 = base[g], b1 = base[g + 1];
         if (b1 == b0) continue;
-        const uint64_t c0 = (b0 + SPAN - 1) / SPAN, c1 = b1 / SPAN;     // whole chunks [c0, c1)
+        const uint64_t c0 = (b0 + F6_SPAN - 1) / F6_SPAN, c1 = b1 / F6_SPAN;    // whole chunks [c0, c1)
         if (c1 <= c0) { add_range(b0, b1, g); continue; }
         if (c1 > 0xffffffffull) return gmg_set_error(GMG_ETOOBIG, "gmg_launch_gene6_groups: batch too large");
-        add_range(b0, c0 * SPAN, g);
-        for (uint64_t c = c0; c < c1; c += KR)
-            rounds.push_back(F6Round{(uint32_t)c, (uint32_t)(c1 - c < KR ? c1 - c : KR) | (uint32_t)g << 5});
-        add_range(c1 * SPAN, b1, g);
+        add_range(b0, c0 * F6_SPAN, g);
+        for (uint64_t c = c0; c < c1; c += F6_K)
+            rounds.push_back(F6Round{(uint32_t)c, (uint32_t)(c1 - c < F6_K ? c1 - c : F6_K) | (uint32_t)g << 5});
+        add_range(c1 * F6_SPAN, b1, g);
     }
     F6Round *d_rounds = nullptr;
     F6Range *d_ranges = nullptr;
@@ -1067,38 +1043,11 @@ int gmg_launch_gene6_groups(const gmg_model *const *models, const uint64_t *grou
     a.n_groups = (uint32_t)n_groups;
 
     if (!rounds.empty()) {
-        int dev = 0, n_cu = 256;
-        GMG_HIP(hipGetDevice(&dev));
-        GMG_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-        unsigned nworkers = (unsigned)(n_cu / 3);
-        if (nworkers < 1) nworkers = 1;
-        if (nworkers > rounds.size()) nworkers = (unsigned)rounds.size();
-        const unsigned grid = 3 * nworkers;
-        const size_t lds = ((size_t)1 << (2 * DT)) * 8;
-        if ((gstride & 1) == 0) {
-            GMG_HIP(hipFuncSetAttribute((const void *)k_frame6t<BLOCK, DT, KR, 0, true, true, false, false, true>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_frame6t<BLOCK, DT, KR, 0, true, true, false, false, true>), dim3(grid), dim3(BLOCK), lds, s, a);
-        } else {
-            GMG_HIP(hipFuncSetAttribute((const void *)k_frame6t<BLOCK, DT, KR, 0, false, true, false, false, true>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_frame6t<BLOCK, DT, KR, 0, false, true, false, false, true>), dim3(grid), dim3(BLOCK), lds, s, a);
-        }
-        GMG_HIP(hipGetLastError());
+        const int rc = f6_launch_main<F6_K, 0, true, false, false, true>(a, rounds.size(), true, s);
+        if (rc) return rc;
     }
-    // the partial-window heads of every read, group by group, and the ranges outside the rounds
-    {
-        const uint64_t blocks = (a.n_reads + 7) / 8;
-        const unsigned grid = (unsigned)(blocks < 256 * 8 ? blocks : 256 * 8);
-        const size_t lds_p = (size_t)3 * a.gene.cstride;
-        a.p_blocks = grid;
-        // (eight blocks per range: with one ICM per read -- up to 2^27 groups -- that would pass the grid limit only at launch time)
-        if ((uint64_t)grid + 8ull * ranges.size() > 0x7fffffffull)
-            return gmg_set_error(GMG_ETOOBIG, "gmg_launch_gene6_groups: %llu group edges in one batch: split the batch", (unsigned long long)ranges.size());
-        hipLaunchKernelGGL((k_frame6p<7, 4, true, true>), dim3(grid + 8 * (unsigned)ranges.size()), dim3(256), lds_p, s, a);
-        GMG_HIP(hipGetLastError());
-    }
-    return GMG_OK;
+    // the partial-window heads of every read, group by group, and the ranges outside the rounds (they cover the batch's tail)
+    return f6_launch_heads<true, true>(a, a.total, s);
 }
 
 // Per-base values of the two strings scoreReadsGlim scores with a periodicity-1 ICM (the read, and its reverse
@@ -1107,45 +1056,14 @@ int gmg_launch_gene6_groups(const gmg_model *const *models, const uint64_t *grou
 // of the batch itself.  *tail_start = first base the main pass did not write.
 int gmg_launch_strings(const gmg_model *m, const gmg_reads *reads, float *d_vals, uint64_t *tail_start, hipStream_t s)
 {
-    if (!(m->dev.has_fast && m->dev.D == 7 && m->dev.W >= 3 && m->dev.W <= 15 && m->dev.P == 1)) return GMG_EBADMODEL;
-    Frame6Args a;
-    a.gene = m->dev;
-    a.nul = m->dev;                                    // not used in gene-only mode
-    a.packed = reads->d_packed;
-    a.off = reads->d_off;
-    a.tile_read = reads->d_tile_read;
-    a.total = reads->total_bases;
-    a.n_reads = reads->n_reads;
-    a.first = 0;
-    a.count = 0;
-    a.out = nullptr;
-    a.stride = 0;
+    if (!(gmg_f6_shape(m->dev) && m->dev.P == 1)) return GMG_EBADMODEL;
+    Frame6Args a = f6_args(m->dev, reads);
     a.out_gene = d_vals;
-    a.gstride = reads->total_bases;
-    a.str_sums = nullptr;
-    a.uniform_len = 0;
-    constexpr int BLOCK = 1024, DT = 7, KR = 16;
-    constexpr uint32_t SPAN = 2 * BLOCK;
-    const uint64_t n_chunks = a.total / SPAN;
-    *tail_start = n_chunks * SPAN;
+    a.gstride = a.total;
+    const uint64_t n_chunks = a.total / F6_SPAN;
+    *tail_start = n_chunks * F6_SPAN;
     if (n_chunks == 0) return GMG_OK;
-    int dev = 0, n_cu = 256;
-    GMG_HIP(hipGetDevice(&dev));
-    GMG_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    unsigned grid = (unsigned)n_cu;                    // one persistent work-group per CU, all on sub-model 0
-    if (grid > n_chunks) grid = (unsigned)n_chunks;
-    const size_t lds = ((size_t)1 << (2 * DT)) * 8;
-    if ((a.total & 1) == 0) {
-        GMG_HIP(hipFuncSetAttribute((const void *)k_frame6t<BLOCK, DT, KR, 0, true, true, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((k_frame6t<BLOCK, DT, KR, 0, true, true, true>), dim3(grid), dim3(BLOCK), lds, s, a);
-    } else {
-        GMG_HIP(hipFuncSetAttribute((const void *)k_frame6t<BLOCK, DT, KR, 0, false, true, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((k_frame6t<BLOCK, DT, KR, 0, false, true, true>), dim3(grid), dim3(BLOCK), lds, s, a);
-    }
-    GMG_HIP(hipGetLastError());
-    return GMG_OK;
+    return f6_launch_main<F6_K, 0, true, true>(a, n_chunks, (a.total & 1) == 0, s);
 }
 
 // The same pass with the values summed per read and string instead of stored (k_frame6t<.., SUM>): d_sums[n_reads][2] must be
@@ -1154,37 +1072,13 @@ int gmg_launch_strings(const gmg_model *m, const gmg_reads *reads, float *d_vals
 // decides per read whether the order of the additions could have mattered, and recomputes the reads where it could.
 int gmg_launch_strings_sum(const gmg_model *m, const gmg_reads *reads, double *d_sums, uint64_t *tail_start, hipStream_t s)
 {
-    if (!(m->dev.has_fast && m->dev.D == 7 && m->dev.W >= 3 && m->dev.W <= 15 && m->dev.P == 1)) return GMG_EBADMODEL;
-    Frame6Args a;
-    a.gene = m->dev;
-    a.nul = m->dev;                                    // not used in gene-only mode
-    a.packed = reads->d_packed;
-    a.off = reads->d_off;
-    a.tile_read = reads->d_tile_read;
-    a.total = reads->total_bases;
-    a.n_reads = reads->n_reads;
-    a.first = 0;
-    a.count = 0;
-    a.out = nullptr;
-    a.stride = 0;
-    a.out_gene = nullptr;
-    a.gstride = 0;
+    if (!(gmg_f6_shape(m->dev) && m->dev.P == 1)) return GMG_EBADMODEL;
+    Frame6Args a = f6_args(m->dev, reads);
     a.str_sums = d_sums;
     a.uniform_len = reads->uniform_len > 0 ? (uint32_t)reads->uniform_len : 0u;
-    constexpr int BLOCK = 1024, DT = 7, KR = 14;      // chunks per round: 10 .. 14 take 1.77 - 1.80 ms per model, 16 (128 registers) 1.91, 8 1.84, 24 2.01
-    constexpr uint32_t SPAN = 2 * BLOCK;
-    const uint64_t n_chunks = a.total / SPAN;
-    *tail_start = n_chunks * SPAN;
+    const uint64_t n_chunks = a.total / F6_SPAN;
+    *tail_start = n_chunks * F6_SPAN;
     if (n_chunks == 0) return GMG_OK;
-    int dev = 0, n_cu = 256;
-    GMG_HIP(hipGetDevice(&dev));
-    GMG_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    unsigned grid = (unsigned)n_cu;                    // one persistent work-group per CU, all on sub-model 0
-    if (grid > n_chunks) grid = (unsigned)n_chunks;
-    const size_t lds = ((size_t)1 << (2 * DT)) * 8;
-    GMG_HIP(hipFuncSetAttribute((const void *)k_frame6t<BLOCK, DT, KR, 0, true, true, true, true>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_frame6t<BLOCK, DT, KR, 0, true, true, true, true>), dim3(grid), dim3(BLOCK), lds, s, a);
-    GMG_HIP(hipGetLastError());
-    return GMG_OK;
+    return f6_launch_main<F6_K_SUM, 0, true, true, true>(a, n_chunks, true, s);     // (nothing is stored: no odd-stride form)
 }
+

@@ -41,6 +41,9 @@ struct GmgDevModel {
     int n_dense_part;
     int has_dense;
 };
+// the shape the six-frame main pass (k_frame6t, gmg_frame6.hip) takes: a completed tree of depth 7 (DEFAULT_MODEL_DEPTH), windows of
+// 3 .. 15 bases.  What else a caller needs (periodicity, the null model's shape) it says next to the call.
+static inline bool gmg_f6_shape(const GmgDevModel &m) { return m.has_fast && m.D == 7 && m.W >= 3 && m.W <= 15; }
 
 struct gmg_model {
     // what the values of the model allow (gmg_strings.hip: sums in any order): the smallest exponent field among the non-zero

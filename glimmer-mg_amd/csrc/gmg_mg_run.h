@@ -372,10 +372,10 @@ static MgPlan mg_plan(const gmg_model *gene, const gmg_model *nul, const MgGroup
     const long long g32_opt = gmg_opt(GMG_OPT_MG_GENE32);
     // (with tiles of two waves or more the GENE32 form wins with one null model as well: ragged 10.6 -> 10.0 ms per 1M x ~400 bp,
     // 500-bp reads 10.9 -> 10.2 ms)
-    bool all_fast = gene->dev.has_fast && gene->dev.D == 7 && gene->dev.W >= 3 && gene->dev.W <= 15;
+    bool all_fast = gmg_f6_shape(gene->dev);
     for (int k = 0; groups && k < groups->n; k++) {
         const GmgDevModel &m = groups->models[k]->dev;
-        all_fast = all_fast && m.has_fast && m.D == 7 && m.W == gene->dev.W;
+        all_fast = all_fast && gmg_f6_shape(m) && m.W == gene->dev.W;
     }
     // (groups of any-shape models: their gene rows come from the exact kernel, group by group -- still the GENE32 form)
     // the error branch on running sums (mg_err_skip) never reads the table itself, only the walk-order sums made from it: the

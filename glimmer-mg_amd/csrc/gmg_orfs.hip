@@ -1126,8 +1126,7 @@ extern "C" int gmg_score_orfs_begin(const gmg_model *gene, const gmg_model *nul,
     hipStream_t s = (hipStream_t)stream;
     gmg_orf_batch *mb = const_cast<gmg_orf_batch *>(b);            // scratch is allocated on first use
     // option orfs_exact_path: 0 = the fastest path the models allow, 1 = the any-shape path, 2 = k_orf_fused even where the events path could run
-    const bool fused = gene->dev.has_fast && gene->dev.D == 7 && gene->dev.P == 3 && gene->dev.W >= 3 && gene->dev.W <= 15 &&
-                       nul->dev.has_dense && nul->dev.W == 3 && nul->dev.P == 3 && gmg_opt(GMG_OPT_ORFS_EXACT_PATH) != 1;
+    const bool fused = gmg_f6_shape(gene->dev) && gene->dev.P == 3 && nul->dev.has_dense && nul->dev.W == 3 && nul->dev.P == 3 && gmg_opt(GMG_OPT_ORFS_EXACT_PATH) != 1;
     // the events path: every sum of the batch exact in any order (the test of gmg_mg.hip's fused kernel; R = longest read + 2)
     bool events = false;
     if (fused && gmg_opt(GMG_OPT_ORFS_EXACT_PATH) == 0) {
