@@ -156,6 +156,7 @@ PROTOTYPES = {
     "gmg_mg_result_fetch_errors": (i32, [vp, vp]),
     "gmg_mg_result_free": (i32, [vp]),
     "gmg_trim_cache": (i32, []),
+    "gmg_debug_owned_blocks": (i32, [C.POINTER(u64)]),
     "gmg_score_reads_strings": (i32, [vp, i32, vp, vp, vp]),
     "gmg_host_register": (i32, [vp, C.c_size_t]),
     "gmg_host_unregister": (i32, [vp]),

@@ -11,6 +11,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <memory>
 #include <new>
 #include <mutex>
 #include <vector>
@@ -359,13 +360,10 @@ extern "C" int gmg_model_upload(const int16_t *mip, const float *prob4, int W, i
             }
         }
 
-    gmg_model *m = new (std::nothrow) gmg_model();
+    std::unique_ptr<gmg_model> m(new (std::nothrow) gmg_model());
     if (!m) return gmg_set_error(GMG_ENOMEM, "gmg_model_upload: out of host memory");
-    hipError_t e = hipMalloc(&m->d_blob, total);
-    if (e != hipSuccess) { delete m; return gmg_set_error(GMG_ENOMEM, "gmg_model_upload: hipMalloc(%zu): %s", total, hipGetErrorString(e)); }
-    e = hipMemcpy(m->d_blob, blob.data(), total, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(m->d_blob); delete m; return gmg_set_error(GMG_EHIP, "gmg_model_upload: hipMemcpy: %s", hipGetErrorString(e)); }
-    m->blob_bytes = total;
+    GMG_HIP(m->own.alloc(&m->d_blob, total));
+    GMG_HIP(hipMemcpy(m->d_blob, blob.data(), total, hipMemcpyHostToDevice));
     m->min_exp = 255;
     m->max_exp = 0;
     m->odd_values = 0;
@@ -382,15 +380,14 @@ extern "C" int gmg_model_upload(const int16_t *mip, const float *prob4, int W, i
         if ((int)ex < m->min_exp) m->min_exp = (int)ex;
         if ((int)ex > m->max_exp) m->max_exp = (int)ex;
     }
-    gmg_model_bind(m, m->d_blob, W, D, P, N, lay);
-    *out = m;
+    gmg_model_bind(m.get(), m->d_blob, W, D, P, N, lay);
+    *out = m.release();
     return GMG_OK;
 }
 
 extern "C" int gmg_model_free(gmg_model *m)
 {
     if (!m) return GMG_OK;
-    if (m->d_blob) (void)hipFree(m->d_blob);
     delete m;
     return GMG_OK;
 }
@@ -414,23 +411,20 @@ extern "C" int gmg_null_set_upload(const gmg_model *const *models, int n, gmg_nu
     for (int i = 0; i < n; i++)
         if (!models[i] || !models[i]->dev.has_dense || models[i]->dev.W != 3 || models[i]->dev.P != 3)
             return gmg_set_error(GMG_EBADMODEL, "gmg_null_set_upload: model %d is not a (3,2,3) Build_Indep_WO_Stops model", i);
-    gmg_null_set *ns = new (std::nothrow) gmg_null_set();
+    std::unique_ptr<gmg_null_set> ns(new (std::nothrow) gmg_null_set());
     if (!ns) return gmg_set_error(GMG_ENOMEM, "gmg_null_set_upload: out of host memory");
-    ns->d_tab = nullptr;
     ns->n = n;
-    ns->min_exp = 255; ns->max_exp = 0; ns->odd_values = 0;
     for (int i = 0; i < n; i++) {
         if (models[i]->min_exp < ns->min_exp) ns->min_exp = models[i]->min_exp;
         if (models[i]->max_exp > ns->max_exp) ns->max_exp = models[i]->max_exp;
         ns->odd_values |= models[i]->odd_values;
     }
-    hipError_t e = hipMalloc((void **)&ns->d_tab, (size_t)n * 252 * sizeof(float));
-    for (int i = 0; i < n && e == hipSuccess; i++) {
-        e = hipMemcpy(ns->d_tab + (size_t)i * 252, models[i]->dev.dense, 192 * sizeof(float), hipMemcpyDeviceToDevice);
-        if (e == hipSuccess) e = hipMemcpy(ns->d_tab + (size_t)i * 252 + 192, models[i]->dev.dense_part, 60 * sizeof(float), hipMemcpyDeviceToDevice);
+    GMG_HIP(ns->own.alloc(&ns->d_tab, (size_t)n * 252 * sizeof(float)));
+    for (int i = 0; i < n; i++) {
+        GMG_HIP(hipMemcpy(ns->d_tab + (size_t)i * 252, models[i]->dev.dense, 192 * sizeof(float), hipMemcpyDeviceToDevice));
+        GMG_HIP(hipMemcpy(ns->d_tab + (size_t)i * 252 + 192, models[i]->dev.dense_part, 60 * sizeof(float), hipMemcpyDeviceToDevice));
     }
-    if (e != hipSuccess) { gmg_null_set_free(ns); return gmg_set_error(GMG_EHIP, "gmg_null_set_upload: %s", hipGetErrorString(e)); }
-    *out = ns;
+    *out = ns.release();
     return GMG_OK;
 }
 
@@ -445,11 +439,9 @@ extern "C" int gmg_null_set_from_tables(const int16_t *mip, const float *prob4, 
     for (size_t i = 0; i < (size_t)n * 63; i++)
         if (mip[i] < -2 || mip[i] > 2)
             return gmg_set_error(GMG_EBADMODEL, "gmg_null_set_from_tables: mut_info_pos %d in model %zu outside [-2,2]", (int)mip[i], i / 63);
-    gmg_null_set *ns = new (std::nothrow) gmg_null_set();
+    std::unique_ptr<gmg_null_set> ns(new (std::nothrow) gmg_null_set());
     if (!ns) return gmg_set_error(GMG_ENOMEM, "gmg_null_set_from_tables: out of host memory");
-    ns->d_tab = nullptr;
     ns->n = n;
-    ns->min_exp = 255; ns->max_exp = 0; ns->odd_values = 0;
     std::vector<float> tab((size_t)n * 252);
     for (int i = 0; i < n; i++)
         for (int p = 0; p < 3; p++) {
@@ -473,17 +465,15 @@ extern "C" int gmg_null_set_from_tables(const int16_t *mip, const float *prob4, 
                 if ((int)ex > ns->max_exp) ns->max_exp = (int)ex;
             }
         }
-    hipError_t e = hipMalloc((void **)&ns->d_tab, tab.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(ns->d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { gmg_null_set_free(ns); return gmg_set_error(GMG_EHIP, "gmg_null_set_from_tables: %s", hipGetErrorString(e)); }
-    *out = ns;
+    GMG_HIP(ns->own.alloc(&ns->d_tab, tab.size() * sizeof(float)));
+    GMG_HIP(hipMemcpy(ns->d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    *out = ns.release();
     return GMG_OK;
 }
 
 extern "C" int gmg_null_set_free(gmg_null_set *ns)
 {
     if (!ns) return GMG_OK;
-    if (ns->d_tab) (void)hipFree(ns->d_tab);
     delete ns;
     return GMG_OK;
 }
@@ -537,6 +527,12 @@ void gmg_reads_set_lengths(gmg_reads *r, const unsigned long long stats[3])
     r->uniform_len = (r->n_reads && stats[0] == stats[1] && stats[0] > 0 && stats[0] < (1u << 30)) ? (int)stats[0] : 0;
 }
 
+// a batch under construction: freed with gmg_reads_free unless the caller gets it (gmg_reads is a plain view, copied by value)
+namespace {
+struct ReadsFree { void operator()(gmg_reads *r) const { (void)gmg_reads_free(r); } };
+typedef std::unique_ptr<gmg_reads, ReadsFree> ReadsGuard;
+}  // namespace
+
 // Packed reads always live in a library-owned buffer with GMG_GUARD_WORDS zero words on both
 // sides, so that window loads around the first and last bases of the job stay inside it.
 static int alloc_packed(gmg_reads *r, const uint32_t *src, hipMemcpyKind kind)
@@ -564,23 +560,21 @@ extern "C" int gmg_reads_upload(const uint32_t *packed, const uint64_t *off, uin
     if (off[0] != 0) return gmg_set_error(GMG_EINVAL, "gmg_reads_upload: base_offsets[0] must be 0");
     uint64_t total = off[n_reads];
     if (total && !packed) return gmg_set_error(GMG_EINVAL, "gmg_reads_upload: NULL packed reads");
-    gmg_reads *r = new (std::nothrow) gmg_reads();
+    ReadsGuard r(new (std::nothrow) gmg_reads());
     if (!r) return gmg_set_error(GMG_ENOMEM, "gmg_reads_upload: out of host memory");
-    memset(r, 0, sizeof *r);
+    memset(r.get(), 0, sizeof *r);
     r->n_reads = n_reads;
     r->total_bases = total;
     r->owns_off = 1;
-    rc = alloc_packed(r, packed, hipMemcpyHostToDevice);
-    if (rc) { gmg_reads_free(r); return rc; }
+    if ((rc = alloc_packed(r.get(), packed, hipMemcpyHostToDevice)) != GMG_OK) return rc;
     uint64_t *d_off = nullptr;
     hipError_t e = hipMalloc((void **)&d_off, (n_reads + 1) * 8);
-    if (e != hipSuccess) { gmg_reads_free(r); return gmg_set_error(GMG_ENOMEM, "gmg_reads_upload: hipMalloc: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return gmg_set_error(GMG_ENOMEM, "gmg_reads_upload: hipMalloc: %s", hipGetErrorString(e));
     r->d_off = d_off;
     e = hipMemcpy(d_off, off, (n_reads + 1) * 8, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { gmg_reads_free(r); return gmg_set_error(GMG_EHIP, "gmg_reads_upload: copy: %s", hipGetErrorString(e)); }
-    rc = finish_reads(r, off);
-    if (rc) { gmg_reads_free(r); return rc; }
-    *out = r;
+    if (e != hipSuccess) return gmg_set_error(GMG_EHIP, "gmg_reads_upload: copy: %s", hipGetErrorString(e));
+    if ((rc = finish_reads(r.get(), off)) != GMG_OK) return rc;
+    *out = r.release();
     return GMG_OK;
 }
 
@@ -591,31 +585,25 @@ extern "C" int gmg_reads_wrap_device(const uint32_t *d_packed, const uint64_t *d
     if (rc) return rc;
     if (!d_off || !out || (total_bases && !d_packed) || n_reads >= 0xffffffffull)
         return gmg_set_error(GMG_EINVAL, "gmg_reads_wrap_device: bad argument");
-    gmg_reads *r = new (std::nothrow) gmg_reads();
+    ReadsGuard r(new (std::nothrow) gmg_reads());
     if (!r) return gmg_set_error(GMG_ENOMEM, "gmg_reads_wrap_device: out of host memory");
-    memset(r, 0, sizeof *r);
+    memset(r.get(), 0, sizeof *r);
     r->d_off = d_off;
     r->n_reads = n_reads;
     r->total_bases = total_bases;
     r->owns_off = 0;
-    rc = alloc_packed(r, d_packed, hipMemcpyDeviceToDevice);   // one on-device copy into a guarded buffer
-    if (rc) { gmg_reads_free(r); return rc; }
+    if ((rc = alloc_packed(r.get(), d_packed, hipMemcpyDeviceToDevice)) != GMG_OK) return rc;   // one on-device copy into a guarded buffer
     // uniform read length is detected from the offsets (a handful of bytes per read, read back once)
     std::vector<uint64_t> h_off(n_reads + 1);
     hipError_t e = hipMemcpy(h_off.data(), d_off, (n_reads + 1) * 8, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { gmg_reads_free(r); return gmg_set_error(GMG_EHIP, "gmg_reads_wrap_device: %s", hipGetErrorString(e)); }
-    if (h_off[0] != 0 || h_off[n_reads] != total_bases) {
-        gmg_reads_free(r);
+    if (e != hipSuccess) return gmg_set_error(GMG_EHIP, "gmg_reads_wrap_device: %s", hipGetErrorString(e));
+    if (h_off[0] != 0 || h_off[n_reads] != total_bases)
         return gmg_set_error(GMG_EINVAL, "gmg_reads_wrap_device: base_offsets do not span [0, total_bases]");
-    }
     for (uint64_t i = 0; i < n_reads; i++)                  // the same checks as gmg_reads_upload: the kernels trust the offsets
-        if (h_off[i + 1] < h_off[i] || h_off[i + 1] - h_off[i] > 0x7fffffffull) {
-            gmg_reads_free(r);
+        if (h_off[i + 1] < h_off[i] || h_off[i + 1] - h_off[i] > 0x7fffffffull)
             return gmg_set_error(GMG_EINVAL, "gmg_reads_wrap_device: base_offsets not monotone at read %llu", (unsigned long long)i);
-        }
-    rc = finish_reads(r, h_off.data());
-    if (rc) { gmg_reads_free(r); return rc; }
-    *out = r;
+    if ((rc = finish_reads(r.get(), h_off.data())) != GMG_OK) return rc;
+    *out = r.release();
     return GMG_OK;
 }
 
@@ -768,48 +756,44 @@ extern "C" int gmg_reads_download(const gmg_reads *r, uint32_t *packed, uint64_t
 // ---------------------------------------------------------------------------
 // one string at a time (the ICM_t methods): persistent staging, no allocation per call
 // ---------------------------------------------------------------------------
-struct gmg_single {
-    gmg_reads reads;
-    gmg_segments segs;
-    uint64_t cap_bases;          // capacity of everything below
-    unsigned char *h_in;         // page-locked: [packed words + guard][off[2]][segment][out_off[2]]
-    unsigned char *d_in;         // the same block on the device, behind GMG_GUARD_WORDS zero words
-    double *h_out, *d_out;       // results (page-locked / device), cap_bases + 16 doubles
-    uint32_t *d_tile_read;       // zeros: every tile lies in read 0
-    bool in_flight;              // a staged copy may still read h_in
+struct GMG_HIDDEN gmg_single {
+    gmg_reads reads = {};
+    gmg_segments segs = {};
+    uint64_t cap_bases = 0;                  // capacity of everything below
+    unsigned char *h_in = nullptr;           // page-locked: [packed words + guard][off[2]][segment][out_off[2]]
+    unsigned char *d_in = nullptr;           // the same block on the device, behind GMG_GUARD_WORDS zero words
+    size_t cap_in = 0, cap_out = 0, cap_tiles = 0;     // bytes at d_in, doubles at d_out, words at d_tile_read
+    double *h_out = nullptr, *d_out = nullptr;         // results (page-locked / device), cap_bases + 16 doubles
+    uint32_t *d_tile_read = nullptr;         // zeros: every tile lies in read 0
+    bool in_flight = false;                  // a staged copy may still read h_in
+    GmgScratch own{GmgScratch::NONE, nullptr, GmgScratch::DRIVER};
+    ~gmg_single() { host_release(); }
+    void host_release()                      // the page-locked pair: not device blocks, freed here and nowhere else
+    {
+        if (h_in) (void)hipHostFree(h_in);
+        if (h_out) (void)hipHostFree(h_out);
+        h_in = nullptr;
+        h_out = nullptr;
+        cap_bases = 0;
+    }
 };
-
-static void single_release(gmg_single *st)
-{
-    if (st->h_in) (void)hipHostFree(st->h_in);
-    if (st->d_in) (void)hipFree(st->d_in);
-    if (st->h_out) (void)hipHostFree(st->h_out);
-    if (st->d_out) (void)hipFree(st->d_out);
-    if (st->d_tile_read) (void)hipFree(st->d_tile_read);
-    st->h_in = st->d_in = nullptr;
-    st->h_out = st->d_out = nullptr;
-    st->d_tile_read = nullptr;
-    st->cap_bases = 0;
-}
 
 static size_t single_words(uint64_t bases) { return (size_t)((bases + 15) / 16 + GMG_GUARD_WORDS); }   // data + trailing guard
 
 static int single_reserve(gmg_single *st, uint64_t n)
 {
-    if (n <= st->cap_bases && st->h_in) return GMG_OK;
-    single_release(st);
+    if (st->cap_bases && n <= st->cap_bases) return GMG_OK;
+    st->host_release();                                 // (cap_bases = 0: a reserve that fails half way is done again by the next call)
     uint64_t cap = 4096;
     while (cap < n) cap *= 2;
-    const size_t in_bytes = single_words(cap) * 4 + 16 + sizeof(gmg_segment) + 16;
-    hipError_t e = hipHostMalloc((void **)&st->h_in, in_bytes, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&st->d_in, GMG_GUARD_WORDS * 4 + in_bytes);
-    if (e == hipSuccess) e = hipMemset(st->d_in, 0, GMG_GUARD_WORDS * 4 + in_bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&st->h_out, (cap + 16) * sizeof(double), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&st->d_out, (cap + 16) * sizeof(double));
-    const size_t tiles = (size_t)(cap / GMG_TILE + 2);
-    if (e == hipSuccess) e = hipMalloc((void **)&st->d_tile_read, tiles * 4);
-    if (e == hipSuccess) e = hipMemset(st->d_tile_read, 0, tiles * 4);
-    if (e != hipSuccess) { single_release(st); return gmg_set_error(GMG_ENOMEM, "gmg_single: %s", hipGetErrorString(e)); }
+    const size_t in_bytes = single_words(cap) * 4 + 16 + sizeof(gmg_segment) + 16, tiles = (size_t)(cap / GMG_TILE + 2);
+    GMG_HIP(hipHostMalloc((void **)&st->h_in, in_bytes, hipHostMallocDefault));
+    GMG_HIP(st->own.regrow(st->d_in, st->cap_in, GMG_GUARD_WORDS * 4 + in_bytes));
+    GMG_HIP(hipMemset(st->d_in, 0, GMG_GUARD_WORDS * 4 + in_bytes));
+    GMG_HIP(hipHostMalloc((void **)&st->h_out, (cap + 16) * sizeof(double), hipHostMallocDefault));
+    GMG_HIP(st->own.regrow(st->d_out, st->cap_out, cap + 16));
+    GMG_HIP(st->own.regrow(st->d_tile_read, st->cap_tiles, tiles));
+    GMG_HIP(hipMemset(st->d_tile_read, 0, tiles * 4));
     st->cap_bases = cap;
     return GMG_OK;
 }
@@ -821,7 +805,6 @@ extern "C" int gmg_single_create(gmg_single **out)
     if (!out) return gmg_set_error(GMG_EINVAL, "gmg_single_create: NULL argument");
     gmg_single *st = new (std::nothrow) gmg_single();
     if (!st) return gmg_set_error(GMG_ENOMEM, "gmg_single_create: out of host memory");
-    memset(st, 0, sizeof *st);
     *out = st;
     return GMG_OK;
 }
@@ -829,7 +812,6 @@ extern "C" int gmg_single_create(gmg_single **out)
 extern "C" int gmg_single_free(gmg_single *st)
 {
     if (!st) return GMG_OK;
-    single_release(st);
     delete st;
     return GMG_OK;
 }
@@ -952,17 +934,22 @@ extern "C" int gmg_segments_upload(const gmg_reads *reads, const gmg_segment *se
         pre[i + 1] = pre[i] + s.len;
         if (s.len < min_len) min_len = s.len;
     }
+    // (a plain view like gmg_reads, copied by value into gmg_single: the two blocks are the call's until the view has them)
+    GmgScratch own(GmgScratch::NONE, nullptr, GmgScratch::DRIVER);
+    gmg_segment *d_segs = nullptr;
+    uint64_t *d_out_off = nullptr;
+    GMG_HIP(own.alloc(&d_segs, (n ? n : 1) * sizeof(gmg_segment)));
+    GMG_HIP(own.alloc(&d_out_off, (n + 1) * 8));
+    if (n) GMG_HIP(hipMemcpy(d_segs, segs, n * sizeof(gmg_segment), hipMemcpyHostToDevice));
+    GMG_HIP(hipMemcpy(d_out_off, pre.data(), (n + 1) * 8, hipMemcpyHostToDevice));
     gmg_segments *g = new (std::nothrow) gmg_segments();
     if (!g) return gmg_set_error(GMG_ENOMEM, "gmg_segments_upload: out of host memory");
-    memset(g, 0, sizeof *g);
+    g->d_segs = d_segs;
+    g->d_out_off = d_out_off;
     g->n = n;
     g->total_len = pre[n];
     g->min_len = min_len;
-    hipError_t e = hipMalloc((void **)&g->d_segs, (n ? n : 1) * sizeof(gmg_segment));
-    if (e == hipSuccess) e = hipMalloc((void **)&g->d_out_off, (n + 1) * 8);
-    if (e == hipSuccess && n) e = hipMemcpy(g->d_segs, segs, n * sizeof(gmg_segment), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(g->d_out_off, pre.data(), (n + 1) * 8, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { gmg_segments_free(g); return gmg_set_error(GMG_EHIP, "gmg_segments_upload: %s", hipGetErrorString(e)); }
+    own.detach(d_segs); own.detach(d_out_off);
     if (out_offsets) memcpy(out_offsets, pre.data(), (n + 1) * 8);
     if (out_total_len) *out_total_len = pre[n];
     *out = g;
@@ -1192,6 +1179,8 @@ void gmg_pool_release_after(void *p, hipStream_t s)
             b.busy = false;
             return;
         }
+    (void)hipStreamSynchronize(s);                      // not ours (as gmg_pool_release): nothing queued uses it once s is idle
+    (void)hipFree(p);
 }
 
 void gmg_pool_release(void *p)
@@ -1201,6 +1190,16 @@ void gmg_pool_release(void *p)
     for (auto &b : g_pool)
         if (b.p == p) { b.busy = false; b.waiting = false; return; }
     (void)hipFree(p);                                   // not ours
+}
+
+// tests: the live device blocks that holders took from hipMalloc and not from the cache (models, null sets, gmg_single,
+// ORF batches, top hits, fixed models).  A handle that is freed holds none.
+std::atomic<long long> g_gmg_owned_blocks{0};
+extern "C" int gmg_debug_owned_blocks(uint64_t *out)
+{
+    if (!out) return gmg_set_error(GMG_EINVAL, "gmg_debug_owned_blocks: NULL argument");
+    *out = (uint64_t)g_gmg_owned_blocks.load();
+    return GMG_OK;
 }
 
 extern "C" int gmg_trim_cache(void)

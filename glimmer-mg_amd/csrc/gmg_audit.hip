@@ -37,12 +37,14 @@ struct AuditArgs {
     int next_stop;                       // GMG_AUDIT_NEXT_STOP
 };
 
-struct gmg_audit {
-    gmg_gene_audit *d_rec;
-    int32_t *d_inner;
-    unsigned long long *d_hist;          // AU_BINS
-    uint64_t n, n_inner;
+struct GMG_HIDDEN gmg_audit {
+    gmg_gene_audit *d_rec = nullptr;
+    int32_t *d_inner = nullptr;
+    unsigned long long *d_hist = nullptr;        // AU_BINS
+    uint64_t n = 0, n_inner = 0;
     hipStream_t s;
+    GmgScratch own;                      // the blocks are free once what is queued on s when the handle goes has run
+    explicit gmg_audit(hipStream_t stream) : s(stream), own(GmgScratch::AFTER, stream) {}
 };
 
 // stats of a call: [0] first bad region
@@ -305,16 +307,13 @@ extern "C" int gmg_genes_audit(const gmg_reads *reads, const gmg_gene_region *re
             GMG_HIP(hipGetLastError());
         }
     }
-    gmg_audit *res = new (std::nothrow) gmg_audit();
+    gmg_audit *res = new (std::nothrow) gmg_audit(s);
     if (!res) return gmg_set_error(GMG_ENOMEM, "gmg_genes_audit: out of host memory");
-    res->d_rec = d_rec;
-    res->d_inner = d_inner;
-    res->d_hist = d_hist;
+    res->d_rec = res->own.take(sc, d_rec);
+    res->d_inner = res->own.take(sc, d_inner);
+    res->d_hist = res->own.take(sc, d_hist);
     res->n = n;
     res->n_inner = total;
-    res->s = s;
-    sc.detach(d_rec); sc.detach(d_hist);
-    if (d_inner) sc.detach(d_inner);
     *out = res;
     return GMG_OK;
 }
@@ -341,9 +340,6 @@ extern "C" int gmg_audit_fetch(const gmg_audit *a, gmg_gene_audit *records, int3
 extern "C" int gmg_audit_free(gmg_audit *a)
 {
     if (!a) return GMG_OK;
-    gmg_pool_release_after(a->d_rec, a->s);
-    gmg_pool_release_after(a->d_hist, a->s);
-    gmg_pool_release_after(a->d_inner, a->s);
     delete a;
     return GMG_OK;
 }

@@ -311,7 +311,7 @@ struct FeatTable {
     std::vector<double> dist[4];                        // index = distance + max_overlap; [3] is folded into [0] by finish()
 };
 
-struct gmg_features {
+struct GMG_HIDDEN gmg_features {
     FeatTable t[2];                                     // GENE, NON
     int32_t max_overlap;
     uint64_t n_records, n_units;
@@ -422,7 +422,7 @@ extern "C" int gmg_features_count(const gmg_reads *reads, const gmg_feature_gene
     // page-locked memory (the whole offset array of a million reads into pageable memory took 30 ms)
     gmg_features *res = new (std::nothrow) gmg_features();
     if (!res) return gmg_set_error(GMG_ENOMEM, "gmg_features_count: out of host memory");
-    struct Guard { gmg_features *p; ~Guard() { delete p; } } guard = {res};
+    std::unique_ptr<gmg_features> guard(res);           // until the caller has it
     memset(res->stage_ms, 0, sizeof res->stage_ms);
     res->max_overlap = max_overlap;
     for (int w = 0; w < 2; w++)
@@ -625,8 +625,7 @@ extern "C" int gmg_features_count(const gmg_reads *reads, const gmg_feature_gene
     res->stage_ms[FEAT_DEV_STAGES] = std::chrono::duration<float, std::milli>(t_device - t_enter).count();
     res->stage_ms[FEAT_DEV_STAGES + 1] = std::chrono::duration<float, std::milli>(t_finish - t_device).count();
     res->stage_ms[FEAT_DEV_STAGES + 2] = std::chrono::duration<float, std::milli>(t_leave - t_finish).count();
-    guard.p = nullptr;
-    *out = res;
+    *out = guard.release();
     return GMG_OK;
 }
 

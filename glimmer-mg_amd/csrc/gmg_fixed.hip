@@ -32,7 +32,7 @@ struct FixedArgs {
     uint32_t nodes[GMG_MAX_MODEL_LEN];     // its node count
 };
 
-struct gmg_fixed_model {
+struct GMG_HIDDEN gmg_fixed_model {
     FixedArgs a;
     int max_depth;
     uint64_t total_nodes;
@@ -40,6 +40,7 @@ struct gmg_fixed_model {
     float4 *d_prob;              // [total_nodes]
     void *d_blob;
     size_t blob_bytes;
+    GmgScratch own{GmgScratch::NONE, nullptr, GmgScratch::DRIVER};
 };
 
 // ---------------------------------------------------------------------------
@@ -186,26 +187,23 @@ extern "C" int gmg_fixed_model_upload(int L, const int32_t *perm, const int16_t 
         memcpy(hp + 4 * (size_t)a.off[i], prob4[i], (size_t)a.nodes[i] * 4 * sizeof(float));
         for (uint32_t k = 0; k < a.nodes[i]; k++) hm[a.off[i] + k] = (int8_t)mip[i][k];
     }
-    gmg_fixed_model *m = new (std::nothrow) gmg_fixed_model();
+    std::unique_ptr<gmg_fixed_model> m(new (std::nothrow) gmg_fixed_model());
     if (!m) return gmg_set_error(GMG_ENOMEM, "gmg_fixed_model_upload: out of host memory");
     m->a = a;
     m->max_depth = max_depth;
     m->total_nodes = total;
     m->blob_bytes = bytes;
-    hipError_t e = hipMalloc(&m->d_blob, bytes);
-    if (e != hipSuccess) { delete m; return gmg_set_error(GMG_ENOMEM, "gmg_fixed_model_upload: hipMalloc(%zu): %s", bytes, hipGetErrorString(e)); }
-    e = hipMemcpy(m->d_blob, h.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(m->d_blob); delete m; return gmg_set_error(GMG_EHIP, "gmg_fixed_model_upload: hipMemcpy: %s", hipGetErrorString(e)); }
+    GMG_HIP(m->own.alloc(&m->d_blob, bytes));
+    GMG_HIP(hipMemcpy(m->d_blob, h.data(), bytes, hipMemcpyHostToDevice));
     m->d_prob = (float4 *)m->d_blob;
     m->d_mip = (int8_t *)((unsigned char *)m->d_blob + total * sizeof(float4));
-    *out = m;
+    *out = m.release();
     return GMG_OK;
 }
 
 extern "C" int gmg_fixed_model_free(gmg_fixed_model *m)
 {
     if (!m) return GMG_OK;
-    if (m->d_blob) (void)hipFree(m->d_blob);
     delete m;
     return GMG_OK;
 }

@@ -544,42 +544,38 @@ extern "C" int gmg_fasta_ingest_on(const char *bytes, uint64_t n_bytes, gmg_read
         bool piecewise = !scans && !timing && (long long)n >= gmg_opt(GMG_OPT_INGEST_PIECE_MIN) && cl.mu.try_lock();
         if (piecewise && !cl.init()) { cl.mu.unlock(); piecewise = false; }
         if (piecewise) {
-            hipError_t pe = hipEventRecord(cl.start, st);                  // (the buffer is ours from here on in `st`'s order)
-            if (pe == hipSuccess) pe = hipStreamWaitEvent(cl.copy, cl.start, 0);
+            // the lane is ours until the block ends; a failure waits for the copies queued so far before the buffers go back
+            struct Lane { FaCopyLane &cl; bool done; ~Lane() { if (!done) (void)hipStreamSynchronize(cl.copy); cl.mu.unlock(); } } lane = {cl, false};
+            GMG_HIP(hipEventRecord(cl.start, st));                         // (the buffer is ours from here on in `st`'s order)
+            GMG_HIP(hipStreamWaitEvent(cl.copy, cl.start, 0));
             // (queued on `st` behind the event: they run beside the first piece's copy)
             rec_cap = n / 16 + 1024;
             const uint64_t words_cap = (n + 15) / 16;
-            if (pe == hipSuccess) pe = dev.alloc(&d_alloc, (words_cap + 2 * GMG_GUARD_WORDS + 1) * 4);
-            if (pe == hipSuccess) pe = dev.alloc(&d_off_big, (rec_cap + 1) * 8);
-            if (pe == hipSuccess) pe = dev.alloc(&d_hb, rec_cap * 8);
-            if (pe == hipSuccess) pe = dev.alloc(&d_he, rec_cap * 8);
-            if (pe == hipSuccess) pe = dev.alloc(&d_gc, 8);
-            if (pe == hipSuccess) pe = hipMemsetAsync(d_alloc, 0, (words_cap + 2 * GMG_GUARD_WORDS + 1) * 4, st);
-            if (pe == hipSuccess) pe = hipMemsetAsync(d_gc, 0, 8, st);
-            if (pe == hipSuccess) {
-                hipLaunchKernelGGL(k_fa_fill, dim3(4096), dim3(256), 0, st, d_he, rec_cap, n_bytes);
-                pe = hipGetLastError();
-                d_packed = d_alloc + GMG_GUARD_WORDS;
-                spec = true;
-            }
+            GMG_HIP(dev.alloc(&d_alloc, (words_cap + 2 * GMG_GUARD_WORDS + 1) * 4));
+            GMG_HIP(dev.alloc(&d_off_big, (rec_cap + 1) * 8));
+            GMG_HIP(dev.alloc(&d_hb, rec_cap * 8));
+            GMG_HIP(dev.alloc(&d_he, rec_cap * 8));
+            GMG_HIP(dev.alloc(&d_gc, 8));
+            GMG_HIP(hipMemsetAsync(d_alloc, 0, (words_cap + 2 * GMG_GUARD_WORDS + 1) * 4, st));
+            GMG_HIP(hipMemsetAsync(d_gc, 0, 8, st));
+            hipLaunchKernelGGL(k_fa_fill, dim3(4096), dim3(256), 0, st, d_he, rec_cap, n_bytes);
+            GMG_HIP(hipGetLastError());
+            d_packed = d_alloc + GMG_GUARD_WORDS;
+            spec = true;
             int k = 0;
-            for (uint64_t b0 = 0; pe == hipSuccess && b0 < n; b0 += piece, k++) {
+            for (uint64_t b0 = 0; b0 < n; b0 += piece, k++) {
                 const uint64_t len = n - b0 < piece ? n - b0 : piece;
-                pe = hipMemcpyAsync(d_bytes + b0, bytes + b0, len, hipMemcpyHostToDevice, cl.copy);
-                if (pe == hipSuccess) pe = hipEventRecord(cl.ev[k], cl.copy);
-                if (pe == hipSuccess) pe = hipStreamWaitEvent(st, cl.ev[k], 0);
-                if (pe == hipSuccess) {
-                    const uint64_t blk0 = b0 / FA_BLK, nb = (len + FA_BLK - 1) / FA_BLK;
-                    hipLaunchKernelGGL(k_fa_summ, dim3((unsigned)(nb < 256 * 16 ? nb : 256 * 16)), dim3(256), 0, st, d_bytes + b0, len, nb, d_summ + blk0);
-                    hipLaunchKernelGGL(k_fa_blocks, dim3(1), dim3(1024), 0, st, d_summ, blk0, blk0 + nb, d_bstate, d_bexcl, d_tot);
-                    FaPack2Args pa = {d_bytes, d_bstate, d_bexcl, n, blk0, blk0 + nb, b0 + len, rec_cap, d_packed, d_off_big, d_hb, d_he, d_gc};
-                    hipLaunchKernelGGL(k_fa_pack2, dim3((unsigned)(nb < 256 * 16 ? nb : 256 * 16)), dim3(256), 0, st, pa);
-                    pe = hipGetLastError();
-                }
+                GMG_HIP(hipMemcpyAsync(d_bytes + b0, bytes + b0, len, hipMemcpyHostToDevice, cl.copy));
+                GMG_HIP(hipEventRecord(cl.ev[k], cl.copy));
+                GMG_HIP(hipStreamWaitEvent(st, cl.ev[k], 0));
+                const uint64_t blk0 = b0 / FA_BLK, nb = (len + FA_BLK - 1) / FA_BLK;
+                hipLaunchKernelGGL(k_fa_summ, dim3((unsigned)(nb < 256 * 16 ? nb : 256 * 16)), dim3(256), 0, st, d_bytes + b0, len, nb, d_summ + blk0);
+                hipLaunchKernelGGL(k_fa_blocks, dim3(1), dim3(1024), 0, st, d_summ, blk0, blk0 + nb, d_bstate, d_bexcl, d_tot);
+                FaPack2Args pa = {d_bytes, d_bstate, d_bexcl, n, blk0, blk0 + nb, b0 + len, rec_cap, d_packed, d_off_big, d_hb, d_he, d_gc};
+                hipLaunchKernelGGL(k_fa_pack2, dim3((unsigned)(nb < 256 * 16 ? nb : 256 * 16)), dim3(256), 0, st, pa);
+                GMG_HIP(hipGetLastError());
             }
-            if (pe != hipSuccess) (void)hipStreamSynchronize(cl.copy);
-            cl.mu.unlock();
-            GMG_HIP(pe);
+            lane.done = true;
         } else
             GMG_HIP(hipMemcpyAsync(d_bytes, bytes, n, hipMemcpyHostToDevice, st));
         lap("copy file to device");

@@ -5,6 +5,9 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
+#include <memory>
+#include <utility>
 #include <vector>
 #include "../../include/gmg.h"
 
@@ -45,14 +48,110 @@ struct GmgDevModel {
 // 3 .. 15 bases.  What else a caller needs (periodicity, the null model's shape) it says next to the call.
 static inline bool gmg_f6_shape(const GmgDevModel &m) { return m.has_fast && m.D == 7 && m.W >= 3 && m.W <= 15; }
 
-struct gmg_model {
+// cache of device blocks for scratch and result buffers (gmg_api.hip): hipMalloc / hipFree of GB-sized buffers cost up
+// to hundreds of milliseconds now and then; a released block is handed to the next request it fits
+void gmg_ingest_trim(void);                       // gmg_ingest.hip: frees its cached page-locked buffers
+hipError_t gmg_pool_alloc(void **out, size_t bytes);
+void gmg_pool_release(void *p);
+void gmg_pool_release_after(void *p, hipStream_t s);   // ... once the work queued on s so far is done
+
+// The device blocks one call or one handle holds, by scope: whatever has not been released early or handed on goes back where it
+// came from when the holder ends -- to the cache, or (DRIVER: the holder's blocks come from hipMalloc) to hipFree, which waits for
+// the device itself.  Where work that uses cached blocks may still be queued the holder waits for the stream (STREAM) or the whole
+// device (DEVICE) first, or -- an asynchronous entry point, a result handle -- leaves the wait to the cache (AFTER: the blocks are
+// free once what is queued on the stream so far has run).  The mode may change during the call.  A handle has ONE holder as a
+// member: its _free is `delete`, and a constructor that fails half way gives everything back by letting go of the handle.
+// (hidden: neither the holder nor a handle type that has one, nor the templates instantiated with them, leave weak symbols among the
+// library's exports)
+#define GMG_HIDDEN __attribute__((visibility("hidden")))
+GMG_HIDDEN extern std::atomic<long long> g_gmg_owned_blocks;   // live DRIVER blocks (gmg_debug_owned_blocks)
+struct GMG_HIDDEN GmgScratch {
+    enum Wait { NONE, STREAM, DEVICE, AFTER };
+    enum Source { CACHE, DRIVER };
+    Wait wait = NONE;
+    hipStream_t st = nullptr;
+    Source from = CACHE;
+    std::vector<void *> v;
+    GmgScratch() {}
+    GmgScratch(Wait w, hipStream_t s, Source f = CACHE) : wait(w), st(s), from(f) {}
+    GmgScratch(const GmgScratch &) = delete;
+    GmgScratch &operator=(const GmgScratch &) = delete;
+    GmgScratch(GmgScratch &&o) : wait(o.wait), st(o.st), from(o.from), v(std::move(o.v)) { o.v.clear(); }   // (handles kept in a std::vector)
+    ~GmgScratch()
+    {
+        if (wait == STREAM) (void)hipStreamSynchronize(st);
+        else if (wait == DEVICE) (void)hipDeviceSynchronize();
+        if (from == DRIVER) g_gmg_owned_blocks -= (long long)v.size();
+        for (void *p : v) give_back(p, wait == AFTER, st);
+    }
+    template <class T> hipError_t alloc(T **p, size_t bytes)
+    {
+        v.reserve(v.size() + 1);                        // (no exception between the allocation and its entry)
+        const hipError_t e = from == DRIVER ? hipMalloc((void **)p, bytes ? bytes : 1) : gmg_pool_alloc((void **)p, bytes);
+        if (e != hipSuccess) { *p = nullptr; return e; }
+        hold(*p);
+        return e;
+    }
+    template <class T> void release(T *&p)              // back now (nothing queued may still use it)
+    {
+        if (!p) return;
+        detach(p);
+        give_back(p, false, nullptr);
+        p = nullptr;
+    }
+    // room for `count` items at p: a block that is too small is replaced, not copied.  The old one goes back as the holder's blocks
+    // do at its end (AFTER: once st has come this far), or, where the caller names the stream whose work may still use it, after that
+    template <class T> hipError_t regrow(T *&p, size_t &cap, size_t count, const hipStream_t *used_on = nullptr)
+    {
+        if (p && cap >= count) return hipSuccess;
+        if (p && detach(p)) give_back(p, used_on || wait == AFTER, used_on ? *used_on : st);
+        p = nullptr;
+        cap = 0;
+        const hipError_t e = alloc(&p, count * sizeof(T));
+        if (e == hipSuccess) cap = count;
+        return e;
+    }
+    // a block of another holder with the same source (the call's) becomes this one's (the result handle's) in one step
+    template <class T> T *take(GmgScratch &other, T *p)
+    {
+        v.reserve(v.size() + 1);
+        if (p && other.detach(p)) hold(p);
+        return p;
+    }
+    bool detach(const void *p)                          // the block is someone else's from here on (a view: gmg_reads)
+    {
+        for (size_t k = 0; k < v.size(); k++)
+            if (v[k] == p) {
+                v[k] = v.back();
+                v.pop_back();
+                if (from == DRIVER) g_gmg_owned_blocks--;
+                return true;
+            }
+        return false;
+    }
+private:
+    void hold(void *p)
+    {
+        v.push_back(p);
+        if (from == DRIVER) g_gmg_owned_blocks++;
+    }
+    void give_back(void *p, bool after, hipStream_t s)
+    {
+        if (from == DRIVER) (void)hipFree(p);
+        else if (after) gmg_pool_release_after(p, s);
+        else gmg_pool_release(p);
+    }
+};
+
+struct GMG_HIDDEN gmg_model {
     // what the values of the model allow (gmg_strings.hip: sums in any order): the smallest exponent field among the non-zero
     // probabilities' logarithms (1 .. 254; 255: all zero), the largest (0: all zero), and whether any value is positive, a NaN
     // or denormal
     int min_exp, max_exp, odd_values;
     GmgDevModel dev;
-    void *d_blob;          // single allocation backing every table
+    void *d_blob;          // single allocation backing every table (the model's own, or a part of its set's block)
     size_t blob_bytes;
+    GmgScratch own{GmgScratch::NONE, nullptr, GmgScratch::DRIVER};
 };
 
 // Byte offsets of a model's tables inside its blob and the sizes they follow from (gmg_model_layout, gmg_api.hip)
@@ -80,18 +179,20 @@ struct gmg_reads {
 };
 
 // gmg_mg_score_reads' result handle (gmg_mg.hip; gmg_entropy.hip reads its ORFs)
-struct gmg_mg_result {
-    gmg_mg_orf *d_orfs;
-    gmg_start *d_starts;
-    gmg_start_errors *d_errs;    // error branch only: parallel to d_starts
-    uint64_t *d_read_orf_off;    // [n_reads + 1]
-    uint64_t n_reads, n_orfs, n_starts;
+struct GMG_HIDDEN gmg_mg_result {
+    gmg_mg_orf *d_orfs = nullptr;
+    gmg_start *d_starts = nullptr;
+    gmg_start_errors *d_errs = nullptr;  // error branch only: parallel to d_starts
+    uint64_t *d_read_orf_off = nullptr;  // [n_reads + 1]
+    uint64_t n_reads = 0, n_orfs = 0, n_starts = 0;
+    GmgScratch own;              // (the caller has waited for the result's stream before it frees the result)
 };
 
-struct gmg_null_set {
-    float *d_tab;                // [n][252]: [3][64] full windows, then [3][20] partial windows of each model
-    int n;
-    int min_exp, max_exp, odd_values;    // over all of its models, as in gmg_model
+struct GMG_HIDDEN gmg_null_set {
+    float *d_tab = nullptr;      // [n][252]: [3][64] full windows, then [3][20] partial windows of each model
+    int n = 0;
+    int min_exp = 255, max_exp = 0, odd_values = 0;      // over all of its models, as in gmg_model
+    GmgScratch own{GmgScratch::NONE, nullptr, GmgScratch::DRIVER};
 };
 
 struct gmg_segments {
@@ -174,54 +275,6 @@ static inline unsigned gmg_grid(uint64_t n_items, uint64_t per_block, uint64_t c
     const uint64_t g = (n_items + per_block - 1) / per_block;
     return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);
 }
-
-// cache of device blocks for scratch and result buffers (gmg_api.hip): hipMalloc / hipFree of GB-sized buffers cost up
-// to hundreds of milliseconds now and then; a released block is handed to the next request it fits
-void gmg_ingest_trim(void);                       // gmg_ingest.hip: frees its cached page-locked buffers
-hipError_t gmg_pool_alloc(void **out, size_t bytes);
-void gmg_pool_release(void *p);
-void gmg_pool_release_after(void *p, hipStream_t s);   // ... once the work queued on s so far is done
-
-// The blocks one call holds, by scope: whatever has not been released early or detached (handed to a result that outlives the
-// call) goes back to the cache when the holder ends.  Where work that uses the blocks may still be queued the holder waits for
-// the stream (STREAM) or the whole device (DEVICE) first, or -- an asynchronous entry point -- leaves the wait to the cache
-// (AFTER: the blocks are free once what is queued on the stream so far has run).  The mode may change during the call.
-struct __attribute__((visibility("hidden"))) GmgScratch {   // (hidden: no weak symbols of it among the library's exports)
-    enum Wait { NONE, STREAM, DEVICE, AFTER };
-    Wait wait = NONE;
-    hipStream_t st = nullptr;
-    std::vector<void *> v;
-    GmgScratch() {}
-    GmgScratch(Wait w, hipStream_t s) : wait(w), st(s) {}
-    GmgScratch(const GmgScratch &) = delete;
-    GmgScratch &operator=(const GmgScratch &) = delete;
-    ~GmgScratch()
-    {
-        if (wait == STREAM) (void)hipStreamSynchronize(st);
-        else if (wait == DEVICE) (void)hipDeviceSynchronize();
-        for (void *p : v)
-            if (wait == AFTER) gmg_pool_release_after(p, st);
-            else gmg_pool_release(p);
-    }
-    template <class T> hipError_t alloc(T **p, size_t bytes)
-    {
-        const hipError_t e = gmg_pool_alloc((void **)p, bytes);
-        if (e == hipSuccess) v.push_back(*p);
-        return e;
-    }
-    template <class T> void detach(T *p)                // the block is someone else's from here on
-    {
-        for (size_t k = 0; k < v.size(); k++)
-            if (v[k] == (void *)p) { v[k] = v.back(); v.pop_back(); return; }
-    }
-    template <class T> void release(T *&p)              // back to the cache now (nothing queued may still use it)
-    {
-        if (!p) return;
-        detach(p);
-        gmg_pool_release(p);
-        p = nullptr;
-    }
-};
 
 // the end of a batch of reads built on the device (gmg_api.hip): its tile table, queued on s; its lengths' statistics from the
 // counters {shortest, longest, reads over 512 bases}

@@ -97,19 +97,15 @@ static unsigned grid_for(uint64_t n)
 // d_off[i] = d_cnt[0] + ... + d_cnt[i-1], i <= n, and *total = d_off[n] (synchronises s): one launch (gmg_scan.h)
 static int mg_scan(uint32_t *d_cnt, uint64_t *d_off, uint64_t n, uint64_t *total, hipStream_t s)
 {
-    hipError_t e = gmg_scan_excl<uint32_t, uint64_t>(d_cnt, d_off, n + 1, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(total, d_off + n, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return gmg_set_error(GMG_EHIP, "gmg_mg_score_reads: scan: %s", hipGetErrorString(e));
+    GMG_HIP((gmg_scan_excl<uint32_t, uint64_t>(d_cnt, d_off, n + 1, s)));
+    GMG_HIP(hipMemcpyAsync(total, d_off + n, 8, hipMemcpyDeviceToHost, s));
+    GMG_HIP(hipStreamSynchronize(s));
     return GMG_OK;
 }
 
 extern "C" int gmg_mg_result_free(gmg_mg_result *r)
 {
     if (!r) return GMG_OK;
-    void *ptrs[] = {r->d_orfs, r->d_starts, r->d_read_orf_off, r->d_errs};
-    for (void *p : ptrs)
-        if (p) gmg_pool_release(p);
     delete r;
     return GMG_OK;
 }
@@ -540,7 +536,6 @@ struct MgRun {
     {
         res = new (std::nothrow) gmg_mg_result();
         if (!res) { sc.wait = GmgScratch::NONE; return gmg_set_error(GMG_ENOMEM, "gmg_mg_score_reads: out of host memory"); }
-        memset(res, 0, sizeof *res);
         res->n_reads = reads->n_reads;
         if (!p.find_only) {                                 // 1. Frame_Scores
             if (prm->nulls && !p.nul_dense3) return gmg_set_error(GMG_EBADMODEL, "gmg_mg_score_reads: per-read null models are (3,2,3) models");
@@ -557,7 +552,7 @@ struct MgRun {
         }
         MG_STAGE(push_order());                             // 5.
         MG_STAGE(finish());
-        sc.detach(res->d_orfs); sc.detach(res->d_starts); sc.detach(res->d_read_orf_off); sc.detach(res->d_errs);
+        res->own.take(sc, res->d_orfs); res->own.take(sc, res->d_starts); res->own.take(sc, res->d_read_orf_off); res->own.take(sc, res->d_errs);
         sc.wait = GmgScratch::NONE;
         *out = res;
         res = nullptr;
@@ -633,19 +628,16 @@ struct MgRun {
         if (n_windows >= 0x7fffffffull) return gmg_set_error(GMG_EINVAL, "gmg_mg_score_reads: batch too large");
         MgTile *d_tiles = nullptr, *d_all = nullptr;
         uint32_t *d_n = nullptr, *d_flag = nullptr;         // d_flag: [n_windows + 1] flags, then [n_windows + 1] their exclusive sums
-        hipError_t e = sc.alloc(&d_all, n_windows * sizeof(MgTile));
-        if (e == hipSuccess) e = sc.alloc(&d_tiles, n_windows * sizeof(MgTile));
-        if (e == hipSuccess) e = sc.alloc(&d_n, 4);
-        if (e == hipSuccess) e = sc.alloc(&d_flag, (2 * (n_windows + 4)) * 4);
-        if (e == hipSuccess) {
-            uint32_t *d_pos = d_flag + ((n_windows + 4) & ~3ull);
-            hipLaunchKernelGGL(k_mg_tile_table, dim3(grid_for(n_windows)), dim3(256), 0, s, a, n_windows, p.cap, d_all);
-            hipLaunchKernelGGL(k_mg_tile_flags, dim3(grid_for(n_windows + 1)), dim3(256), 0, s, d_all, n_windows, d_flag);
-            e = gmg_scan_excl<uint32_t, uint32_t>(d_flag, d_pos, n_windows + 1, s);
-            if (e == hipSuccess) hipLaunchKernelGGL(k_mg_tile_compact, dim3(grid_for(n_windows)), dim3(256), 0, s, d_all, n_windows, d_pos, d_tiles, d_n);
-            if (e == hipSuccess) e = hipGetLastError();
-        }
-        if (e != hipSuccess) return gmg_set_error(GMG_EHIP, "gmg_mg_score_reads: tile table: %s", hipGetErrorString(e));
+        MG_TRY(sc.alloc(&d_all, n_windows * sizeof(MgTile)));
+        MG_TRY(sc.alloc(&d_tiles, n_windows * sizeof(MgTile)));
+        MG_TRY(sc.alloc(&d_n, 4));
+        MG_TRY(sc.alloc(&d_flag, (2 * (n_windows + 4)) * 4));
+        uint32_t *d_pos = d_flag + ((n_windows + 4) & ~3ull);
+        hipLaunchKernelGGL(k_mg_tile_table, dim3(grid_for(n_windows)), dim3(256), 0, s, a, n_windows, p.cap, d_all);
+        hipLaunchKernelGGL(k_mg_tile_flags, dim3(grid_for(n_windows + 1)), dim3(256), 0, s, d_all, n_windows, d_flag);
+        MG_TRY((gmg_scan_excl<uint32_t, uint32_t>(d_flag, d_pos, n_windows + 1, s)));
+        hipLaunchKernelGGL(k_mg_tile_compact, dim3(grid_for(n_windows)), dim3(256), 0, s, d_all, n_windows, d_pos, d_tiles, d_n);
+        MG_TRY(hipGetLastError());
         a.tiles = d_tiles;
         a.windows = d_all;
         a.n_tiles_dev = d_n;
@@ -755,15 +747,14 @@ struct MgRun {
     }
 
     // Set_Quality_454 / Clean_Quality_454: needs the reads only
-    hipError_t build_qualities(hipStream_t st)
+    int build_qualities(hipStream_t st)
     {
-        hipError_t e = hipSuccess;
-        if (prm->quality) e = hipMemcpyAsync(d_user_q, prm->quality, a.total, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && !d_walk_q) e = sc.alloc(&d_walk_q, a.total + 8);
-        if (e != hipSuccess) return e;
+        if (prm->quality) MG_TRY(hipMemcpyAsync(d_user_q, prm->quality, a.total, hipMemcpyHostToDevice, st));
+        if (!d_walk_q) MG_TRY(sc.alloc(&d_walk_q, a.total + 8));
         hipLaunchKernelGGL(k_mg_quality, dim3(grid_for(nr * 64)), dim3(256), 0, st, a, d_user_q, d_qual + 64, d_walk_q);
         a.walk_q = d_walk_q;
-        return hipGetLastError();
+        MG_TRY(hipGetLastError());
+        return GMG_OK;
     }
 
     // ORF discovery: count, scan, write (one lane per read / events / bit masks / the general form with ignore regions and circular sequences)
@@ -774,7 +765,7 @@ struct MgRun {
         // kernel's shadow: no LDS, few registers)
         a.q454 = p.q454;
         if (p.err_mode == 1 && a.total && !p.find_only && !a.q454) {
-            MG_TRY(build_qualities(s3));
+            MG_STAGE(build_qualities(s3));
             tm.lap("quality values");
         }
         MG_TRY(sc.alloc(&d_read_cnt, (nr + 1) * 4));
@@ -839,21 +830,20 @@ struct MgRun {
     }
 
     // the run lengths of the level kernels' walks (they need the reads and the qualities only)
-    hipError_t build_run_tables(hipStream_t st)
+    int build_run_tables(hipStream_t st)
     {
-        hipError_t e = sc.alloc(&d_run, (size_t)4 * a.walk_stride);
-        if (e != hipSuccess) return e;
+        MG_TRY(sc.alloc(&d_run, (size_t)4 * a.walk_stride));
         a.run_q = d_run; a.run_n = d_run + 2 * a.walk_stride;
         hipLaunchKernelGGL(k_mg_run_tables, dim3(grid_for(2 * nr * 64)), dim3(256), 0, st, a, d_run, d_run + 2 * a.walk_stride);
-        return hipGetLastError();
+        MG_TRY(hipGetLastError());
+        return GMG_OK;
     }
 
     // the walk-order rows of the level kernels (running sums, or the values themselves): behind the six-frame table on stream st
-    hipError_t build_walk_rows(hipStream_t st)
+    int build_walk_rows(hipStream_t st)
     {
         a.qonly = a.pfx && p.qonly ? 1 : 0;
-        hipError_t e = sc.alloc(&d_walk, ((size_t)(a.qonly ? 2 : 6) * a.walk_stride + 8) * sizeof(double));
-        if (e != hipSuccess) return e;
+        MG_TRY(sc.alloc(&d_walk, ((size_t)(a.qonly ? 2 : 6) * a.walk_stride + 8) * sizeof(double)));
         if (a.qonly) {
             // (tried: the same table codon by codon -- a lane on three consecutive steps, ONE scan per class per 192 steps instead of
             // per 64: bit-exact, 23.5 against 22.0 ms per 1M reads with -s: the loads of a lane's three steps no longer coalesce)
@@ -865,7 +855,8 @@ struct MgRun {
         } else
             hipLaunchKernelGGL(k_mg_walk_tables, dim3(grid_for(a.total)), dim3(256), 0, st, a, d_walk + 8);
         a.walk = d_walk + 8;                            // (8 spare entries in front: a call at the table's first entry looks one back)
-        return hipGetLastError();
+        MG_TRY(hipGetLastError());
+        return GMG_OK;
     }
 
     // the error branch's walk-order tables, unless the wave / tile kernels build them in LDS
@@ -877,8 +868,8 @@ struct MgRun {
             // (second stream), the six-frame kernel and the rows.  Tile by tile (k_mg_err_tile) the rows are built in LDS, tile by tile.
             a.walk_stride = ((a.total + 15) & ~15ull) + 16;
             a.pfx = p.pfx;
-            if (a.pfx && !p.err_tile && !p.err_wave) MG_TRY(build_run_tables(s3));   // running sums + run lengths: the walks visit their events only
-            if (!p.err_tile && !p.err_wave) MG_TRY(build_walk_rows(s));
+            if (a.pfx && !p.err_tile && !p.err_wave) MG_STAGE(build_run_tables(s3));   // running sums + run lengths: the walks visit their events only
+            if (!p.err_tile && !p.err_wave) MG_STAGE(build_walk_rows(s));
             MG_TRY(hipGetLastError());
             tm.lap("walk-order tables");
         }
@@ -886,30 +877,30 @@ struct MgRun {
     }
 
     // the level kernels' scratch: call arrays, per-ORF aggregates, slot counters
-    hipError_t alloc_level_scratch()
+    int alloc_level_scratch()
     {
         a.call_cap = a.total / 2 > 65536 ? a.total / 2 : 65536;
         const uint64_t hinted = (uint64_t)(tl_mg_calls_per_base_hint * 1.15 * (double)a.total) + 65536;
         if (hinted > a.call_cap && hinted <= 8 * a.total + 65536) a.call_cap = hinted;
         if (gmg_opt(GMG_OPT_MG_ERR_CALLS) > 0) a.call_cap = (uint64_t)gmg_opt(GMG_OPT_MG_ERR_CALLS);     // (tests: force the fallback)
-        hipError_t e = sc.alloc(&d_calls[0], a.call_cap * sizeof(MgCall));
-        if (e == hipSuccess) e = sc.alloc(&d_calls[1], a.call_cap * sizeof(MgCall));
-        if (e == hipSuccess) e = sc.alloc(&d_agg, no * sizeof(MgOrfAgg));
-        if (e == hipSuccess) e = sc.alloc(&d_fill, no * 4);
+        MG_TRY(sc.alloc(&d_calls[0], a.call_cap * sizeof(MgCall)));
+        MG_TRY(sc.alloc(&d_calls[1], a.call_cap * sizeof(MgCall)));
+        MG_TRY(sc.alloc(&d_agg, no * sizeof(MgOrfAgg)));
+        MG_TRY(sc.alloc(&d_fill, no * 4));
         a.calls[0] = d_calls[0]; a.calls[1] = d_calls[1]; a.agg = d_agg; a.fill = d_fill;
-        return e;
+        return GMG_OK;
     }
 
-    hipError_t alloc_staging(uint64_t entries)
+    int alloc_staging(uint64_t entries)
     {
         sc.release(d_st_s);
         sc.release(d_st_e);
         sc.release(d_st_k);
         et_stage_cap = entries;
-        hipError_t e = sc.alloc(&d_st_s, entries * sizeof(gmg_start));
-        if (e == hipSuccess) e = sc.alloc(&d_st_e, entries * sizeof(gmg_start_errors));
-        if (e == hipSuccess) e = sc.alloc(&d_st_k, entries * 8);
-        return e;
+        MG_TRY(sc.alloc(&d_st_s, entries * sizeof(gmg_start)));
+        MG_TRY(sc.alloc(&d_st_e, entries * sizeof(gmg_start_errors)));
+        MG_TRY(sc.alloc(&d_st_k, entries * 8));
+        return GMG_OK;
     }
 
     // the error branch's flags and counters, and the scratch of whichever kernel family takes the batch
@@ -942,8 +933,8 @@ struct MgRun {
             // what leaves the tiles: the accepted ORFs' starts (measured: one per 52 bases of 454-like reads) or every start (one per 4)
             uint64_t want = (p.err_acc_only ? a.total / 16 : a.total / 3) + (1u << 20);
             if (gmg_opt(GMG_OPT_MG_ERR_TILE_Q) != 0) want = 64;         // (tests; -1: only this: the first pass finds the arrays too small)
-            MG_TRY(alloc_staging(want));
-        } else if (!p.err_wave) MG_TRY(alloc_level_scratch());
+            MG_STAGE(alloc_staging(want));
+        } else if (!p.err_wave) MG_STAGE(alloc_level_scratch());
         if (p.err_wave) MG_TRY(sc.alloc(&d_item_flag, 2 * nr + 64));
         return GMG_OK;
     }
@@ -1146,13 +1137,13 @@ struct MgRun {
             // the staging arrays were too small: once more with what the kernel asked for (every batch of ORFs has added its wish)
             unsigned long long asked = 0;
             memcpy(&asked, st + 22, 8);
-            MG_TRY(alloc_staging(asked + 1024));
+            MG_STAGE(alloc_staging(asked + 1024));
         } else if (err_tile || err_wave) {
             p.to_level_kernels();
-            if (a.q454) { a.q454 = p.q454; MG_TRY(build_qualities(s2)); }
-            if (a.pfx) MG_TRY(build_run_tables(s2));
-            MG_TRY(build_walk_rows(s2));
-            MG_TRY(alloc_level_scratch());
+            if (a.q454) { a.q454 = p.q454; MG_STAGE(build_qualities(s2)); }
+            if (a.pfx) MG_STAGE(build_run_tables(s2));
+            MG_STAGE(build_walk_rows(s2));
+            MG_STAGE(alloc_level_scratch());
         } else {
             // once more with arrays of twice what was asked for (level 2 is only partly known when level 1 overflows); if that is
             // not enough either, or does not fit, everything runs on the per-ORF kernel
@@ -1264,58 +1255,49 @@ struct MgRun {
         // Error branch: the write passes put an ORF's starts at the scan of the counts, and a rejected ORF counts 0 -- the start,
         // error and key arrays hold the accepted ORFs' lists alone, in order: packed already.  Only the records move.
         const bool starts_packed = err_mode != 0;
-        hipError_t e = sc.alloc(&d_keep, (no + 1) * 4);
-        if (e == hipSuccess && !starts_packed) e = sc.alloc(&d_keep_st, (no + 1) * 4);
-        if (e == hipSuccess) e = sc.alloc(&d_new_orf, (no + 1) * 8);
-        if (e == hipSuccess && !starts_packed) e = sc.alloc(&d_new_st, (no + 1) * 8);
-        if (e == hipSuccess) e = sc.alloc(&d_new_first, (nr + 1) * 8);
-        if (e == hipSuccess) e = hipMemsetAsync(d_keep + no, 0, 4, s);
-        if (e == hipSuccess && !starts_packed) e = hipMemsetAsync(d_keep_st + no, 0, 4, s);
-        int rc2 = GMG_OK;
+        MG_TRY(sc.alloc(&d_keep, (no + 1) * 4));
+        if (!starts_packed) MG_TRY(sc.alloc(&d_keep_st, (no + 1) * 4));
+        MG_TRY(sc.alloc(&d_new_orf, (no + 1) * 8));
+        if (!starts_packed) MG_TRY(sc.alloc(&d_new_st, (no + 1) * 8));
+        MG_TRY(sc.alloc(&d_new_first, (nr + 1) * 8));
+        MG_TRY(hipMemsetAsync(d_keep + no, 0, 4, s));
+        if (!starts_packed) MG_TRY(hipMemsetAsync(d_keep_st + no, 0, 4, s));
         // (error branch: the bitmap of the accepted ORFs is complete unless everything went to the per-ORF kernel)
         const uint32_t *kept_bits = (err_mode && err_path == 0) ? d_acc_bits : nullptr;
-        if (e == hipSuccess && starts_packed && kept_bits && no) {
+        if (starts_packed && kept_bits && no) {
             const uint64_t n_words = no / 32 + 1;
             uint32_t *d_wc = nullptr, n_keep32 = 0;       // [n_words + 1] set bits per word, then [n_words + 1] their exclusive sums
-            e = sc.alloc(&d_wc, 2 * (n_words + 4) * 4);
-            uint32_t *d_wo = d_wc ? d_wc + ((n_words + 4) & ~3ull) : nullptr;
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(k_mg_keep_words, dim3(grid_for(n_words + 1)), dim3(256), 0, s, kept_bits, n_words, d_wc);
-                e = gmg_scan_excl<uint32_t, uint32_t>(d_wc, d_wo, n_words + 1, s);
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(&n_keep32, d_wo + n_words, 4, hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            MG_TRY(sc.alloc(&d_wc, 2 * (n_words + 4) * 4));
+            uint32_t *d_wo = d_wc + ((n_words + 4) & ~3ull);
+            hipLaunchKernelGGL(k_mg_keep_words, dim3(grid_for(n_words + 1)), dim3(256), 0, s, kept_bits, n_words, d_wc);
+            MG_TRY((gmg_scan_excl<uint32_t, uint32_t>(d_wc, d_wo, n_words + 1, s)));
+            MG_TRY(hipMemcpyAsync(&n_keep32, d_wo + n_words, 4, hipMemcpyDeviceToHost, s));
+            MG_TRY(hipStreamSynchronize(s));
             n_keep = n_keep32;
             n_keep_st = res->n_starts;
-            if (e == hipSuccess) e = sc.alloc(&d_orfs2, (n_keep ? n_keep : 1) * sizeof(gmg_mg_orf));
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(k_mg_keep_gather_bits, dim3(grid_for(n_words)), dim3(256), 0, s, res->d_orfs, kept_bits, d_wo, n_words, no, d_orfs2);
-                hipLaunchKernelGGL(k_mg_keep_reads_bits, dim3(grid_for(nr + 1)), dim3(256), 0, s, res->d_read_orf_off, nr, kept_bits, d_wo, d_new_first);
-                e = hipGetLastError();
-                if (e == hipSuccess) e = hipStreamSynchronize(s);
-            }
+            MG_TRY(sc.alloc(&d_orfs2, (n_keep ? n_keep : 1) * sizeof(gmg_mg_orf)));
+            hipLaunchKernelGGL(k_mg_keep_gather_bits, dim3(grid_for(n_words)), dim3(256), 0, s, res->d_orfs, kept_bits, d_wo, n_words, no, d_orfs2);
+            hipLaunchKernelGGL(k_mg_keep_reads_bits, dim3(grid_for(nr + 1)), dim3(256), 0, s, res->d_read_orf_off, nr, kept_bits, d_wo, d_new_first);
+            MG_TRY(hipGetLastError());
+            MG_TRY(hipStreamSynchronize(s));
             sc.release(d_wc);
-        } else if (e == hipSuccess) {
+        } else {
             if (no) hipLaunchKernelGGL(k_mg_keep_counts, dim3(grid_for(no)), dim3(256), 0, s, res->d_orfs, kept_bits, no, d_keep, d_keep_st);
-            rc2 = mg_scan(d_keep, d_new_orf, no, &n_keep, s);
+            MG_STAGE(mg_scan(d_keep, d_new_orf, no, &n_keep, s));
             if (starts_packed) n_keep_st = res->n_starts;
-            else if (!rc2) rc2 = mg_scan(d_keep_st, d_new_st, no, &n_keep_st, s);
-            if (!rc2) e = sc.alloc(&d_orfs2, (n_keep ? n_keep : 1) * sizeof(gmg_mg_orf));
-            if (!rc2 && e == hipSuccess && !starts_packed) e = sc.alloc(&d_starts2, (n_keep_st ? n_keep_st : 1) * sizeof(gmg_start));
-            if (!rc2 && e == hipSuccess) {
-                if (no) hipLaunchKernelGGL(k_mg_keep_gather, dim3(grid_for(no)), dim3(256), 0, s, res->d_orfs, kept_bits, res->d_starts, no, d_new_orf,
-                                           starts_packed ? (const uint64_t *)nullptr : d_new_st, d_orfs2, d_starts2);
-                hipLaunchKernelGGL(k_mg_keep_reads, dim3(grid_for(nr + 1)), dim3(256), 0, s, res->d_read_orf_off, nr, d_new_orf, d_new_first);
-                e = hipGetLastError();
-                if (e == hipSuccess) e = hipStreamSynchronize(s);
-            }
+            else MG_STAGE(mg_scan(d_keep_st, d_new_st, no, &n_keep_st, s));
+            MG_TRY(sc.alloc(&d_orfs2, (n_keep ? n_keep : 1) * sizeof(gmg_mg_orf)));
+            if (!starts_packed) MG_TRY(sc.alloc(&d_starts2, (n_keep_st ? n_keep_st : 1) * sizeof(gmg_start)));
+            if (no) hipLaunchKernelGGL(k_mg_keep_gather, dim3(grid_for(no)), dim3(256), 0, s, res->d_orfs, kept_bits, res->d_starts, no, d_new_orf,
+                                       starts_packed ? (const uint64_t *)nullptr : d_new_st, d_orfs2, d_starts2);
+            hipLaunchKernelGGL(k_mg_keep_reads, dim3(grid_for(nr + 1)), dim3(256), 0, s, res->d_read_orf_off, nr, d_new_orf, d_new_first);
+            MG_TRY(hipGetLastError());
+            MG_TRY(hipStreamSynchronize(s));
         }
         sc.release(d_keep);
         sc.release(d_keep_st);
         sc.release(d_new_orf);
         sc.release(d_new_st);
-        if (rc2) return rc2;
-        if (e != hipSuccess) return gmg_set_error(GMG_EHIP, "gmg_mg_score_reads: packing the accepted ORFs: %s", hipGetErrorString(e));
         sc.release(res->d_orfs);
         sc.release(res->d_read_orf_off);
         if (!starts_packed) { sc.release(res->d_starts); res->d_starts = d_starts2; }     // (else: starts, errors and keys stay where they are)
@@ -1333,17 +1315,13 @@ struct MgRun {
         const uint64_t ns = res->n_starts, nseg = res->n_orfs;
         gmg_start *d_starts3 = nullptr;
         gmg_start_errors *d_errs3 = nullptr;
-        hipError_t e = sc.alloc(&d_starts3, ns * sizeof(gmg_start));
-        if (e == hipSuccess) e = sc.alloc(&d_errs3, ns * sizeof(gmg_start_errors));
-        if (e == hipSuccess) {
-            const uint64_t blocks = (nseg + 3) / 4;
-            hipLaunchKernelGGL(k_mg_order_starts, dim3((unsigned)(blocks < 256 * 32 ? blocks : 256 * 32)), dim3(256), 0, s, res->d_orfs, nseg, d_keys, res->d_starts,
-                               res->d_errs, d_starts3, d_errs3);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess)
-            return gmg_set_error(e == hipErrorOutOfMemory ? GMG_ENOMEM : GMG_EHIP, "gmg_mg_score_reads: ordering the start lists: %s", hipGetErrorString(e));
+        MG_TRY(sc.alloc(&d_starts3, ns * sizeof(gmg_start)));
+        MG_TRY(sc.alloc(&d_errs3, ns * sizeof(gmg_start_errors)));
+        const uint64_t blocks = (nseg + 3) / 4;
+        hipLaunchKernelGGL(k_mg_order_starts, dim3((unsigned)(blocks < 256 * 32 ? blocks : 256 * 32)), dim3(256), 0, s, res->d_orfs, nseg, d_keys, res->d_starts,
+                           res->d_errs, d_starts3, d_errs3);
+        MG_TRY(hipGetLastError());
+        MG_TRY(hipStreamSynchronize(s));
         sc.release(res->d_starts);
         sc.release(res->d_errs);
         res->d_starts = d_starts3;

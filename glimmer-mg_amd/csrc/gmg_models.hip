@@ -265,19 +265,21 @@ bool shape_ok(int W, int D, int P, int N, char *msg, size_t msg_len)
 
 }  // namespace
 
-struct gmg_model_set {
-    int n;
+struct GMG_HIDDEN gmg_model_set {
+    int n = 0;
     hipStream_t stream;
-    unsigned char *d_block;      // descriptors, status words, every blob
-    size_t status_off;
+    unsigned char *d_block = nullptr;    // descriptors, status words, every blob
+    size_t status_off = 0;
     std::vector<gmg_model> models;
     std::vector<MsDesc> desc;
     std::vector<const unsigned char *> bytes;           // the caller's buffers: read again for the message of a refusal
     std::vector<unsigned char> h_head;                  // descriptors + initial status words as they went up
     std::vector<uint32_t> h_status;
-    bool finished;
-    int rc, bad_file;
+    bool finished = false;
+    int rc = GMG_OK, bad_file = -1;
     std::string message;
+    GmgScratch own;              // the block is free once what is queued on the load stream when the set goes has run
+    explicit gmg_model_set(hipStream_t s) : stream(s), own(GmgScratch::AFTER, s) {}
 };
 
 extern "C" int gmg_icm_bytes_info(const void *bytes, uint64_t n_bytes, int *model_len, int *model_depth, int *periodicity, int *num_nodes,
@@ -306,15 +308,10 @@ extern "C" int gmg_model_set_load(const void *const *bytes, const uint64_t *n_by
     if (!bytes || !n_bytes || !out || n_files < 1 || n_files > 65535)
         return gmg_set_error(GMG_EINVAL, "gmg_model_set_load: bad argument (1 .. 65535 files per call)");
     hipStream_t s = (hipStream_t)stream;
-    gmg_model_set *set = new (std::nothrow) gmg_model_set();
+    gmg_model_set *set = new (std::nothrow) gmg_model_set(s);
     if (!set) return gmg_set_error(GMG_ENOMEM, "gmg_model_set_load: out of host memory");
     std::unique_ptr<gmg_model_set> own(set);            // until the caller has it
     set->n = n_files;
-    set->stream = s;
-    set->d_block = nullptr;
-    set->finished = false;
-    set->rc = GMG_OK;
-    set->bad_file = -1;
     set->models.resize(n_files);
     set->desc.resize(n_files);
     set->bytes.resize(n_files);
@@ -414,8 +411,7 @@ extern "C" int gmg_model_set_load(const void *const *bytes, const uint64_t *n_by
         hipLaunchKernelGGL(k_ms_flatten, dim3(grid_x(max_flat), n_files), dim3(MS_BLOCK), 0, s, d_desc, blk);
         GMG_HIP(hipGetLastError());
     }
-    set->d_block = blk;
-    sc.detach(blk);
+    set->d_block = set->own.take(sc, blk);
     sc.wait = GmgScratch::AFTER;
     for (int k = 0; k < n_files; k++) {
         const MsDesc &d = set->desc[k];
@@ -503,19 +499,16 @@ extern "C" const gmg_model *gmg_model_set_model(const gmg_model_set *set, int k)
 extern "C" int gmg_model_set_free(gmg_model_set *set)
 {
     if (!set) return GMG_OK;
-    if (set->d_block) {
-        // The block may be handed out again once the load stream reaches this point.  What scores with the models was queued by the
-        // caller, by default on the null stream: the load stream is made to wait for that one too, on the device -- the host does not
-        // block.  (A set used on further streams is the caller's to wait for, as with gmg_model_free.)
-        if (!set->finished) (void)hipStreamSynchronize(set->stream);       // (the status copy of a _finish never made: nothing reads h_status later)
-        hipEvent_t ev = nullptr;
-        if (set->stream != nullptr) {
-            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess && hipEventRecord(ev, 0) == hipSuccess &&
-                hipStreamWaitEvent(set->stream, ev, 0) == hipSuccess) { /* ordered on the device */ }
-            else (void)hipStreamSynchronize(0);
-            if (ev) (void)hipEventDestroy(ev);
-        }
-        gmg_pool_release_after(set->d_block, set->stream);
+    // The block may be handed out again once the load stream reaches this point.  What scores with the models was queued by the
+    // caller, by default on the null stream: the load stream is made to wait for that one too, on the device -- the host does not
+    // block.  (A set used on further streams is the caller's to wait for, as with gmg_model_free.)
+    if (!set->finished) (void)hipStreamSynchronize(set->stream);           // (the status copy of a _finish never made: nothing reads h_status later)
+    hipEvent_t ev = nullptr;
+    if (set->stream != nullptr) {
+        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess && hipEventRecord(ev, 0) == hipSuccess &&
+            hipStreamWaitEvent(set->stream, ev, 0) == hipSuccess) { /* ordered on the device */ }
+        else (void)hipStreamSynchronize(0);
+        if (ev) (void)hipEventDestroy(ev);
     }
     delete set;
     return GMG_OK;

@@ -17,29 +17,29 @@
 
 struct OrfTmp { double s; int32_t which, pad; };   // one in-frame position of the ascending pass
 
-struct gmg_orf_batch {
-    double *d_walk;              // events path: running sums in walking order, [2][total_bases] (allocated on first use)
-    uint32_t *d_heads;           // ... and one bit per base and strand: an ORF asks for the sum there (its HEAD position), [2][total_bases / 32 + 4]
-    uint16_t *d_qpre;            // ... compact form: per lane of every unit the values in front of its own, [2][total_bases / 8 + n_reads + 64]
-    uint8_t *d_qneed;            // ... and its need bits
-    float *d_gene6;              // fused / events path: per-base gene values, [6][total_bases] (allocated on first use)
-    OrfTmp *d_tmp;               // fused path: one slot per in-frame position, same offsets as the start lists
-    gmg_orf *d_orfs;
-    gmg_segments *segs;          // the ORF buffers as segments (REVERSED / COMPLEMENTED)
-    uint64_t *d_start_off;       // [n+1] first slot of each ORF's start list
-    double *d_score, *d_indep;   // cumulative scores, segs->total_len each
-    gmg_orf_result *d_results;
-    gmg_start *d_starts;         // one region of orf_len/3+2 slots per ORF, filled from its front
-    uint32_t *d_nst, *d_coff;    // [n+1] starts per ORF and their exclusive prefix sum (compaction)
-    void *d_scan_tmp;
-    size_t scan_tmp_bytes;
-    gmg_start *d_compact;        // the used slots back to back: what leaves the GPU (grown on demand)
-    uint64_t compact_cap;
-    uint64_t n, max_starts;
-    uint64_t n_packed;           // starts of the last gmg_score_orfs_begin, back to back in d_compact
-    int scored;
-    const gmg_reads *reads;      // the batch the ORFs were validated against (gmg_orfs_upload): gmg_score_orfs takes no other
-    uint64_t reads_total;
+struct GMG_HIDDEN gmg_orf_batch {
+    double *d_walk = nullptr;    // events path: running sums in walking order, [2][total_bases] (allocated on first use)
+    uint32_t *d_heads = nullptr; // ... and one bit per base and strand: an ORF asks for the sum there (its HEAD position), [2][total_bases / 32 + 4]
+    uint16_t *d_qpre = nullptr;  // ... compact form: per lane of every unit the values in front of its own, [2][total_bases / 8 + n_reads + 64]
+    uint8_t *d_qneed = nullptr;  // ... and its need bits
+    float *d_gene6 = nullptr;    // fused / events path: per-base gene values, [6][total_bases] (allocated on first use)
+    OrfTmp *d_tmp = nullptr;     // fused path: one slot per in-frame position, same offsets as the start lists
+    gmg_orf *d_orfs = nullptr;
+    gmg_segments *segs = nullptr;        // the ORF buffers as segments (REVERSED / COMPLEMENTED)
+    uint64_t *d_start_off = nullptr;     // [n+1] first slot of each ORF's start list
+    double *d_score = nullptr, *d_indep = nullptr;       // cumulative scores, segs->total_len each
+    gmg_orf_result *d_results = nullptr;
+    gmg_start *d_starts = nullptr;       // one region of orf_len/3+2 slots per ORF, filled from its front
+    uint32_t *d_nst = nullptr, *d_coff = nullptr;        // [n+1] starts per ORF and their exclusive prefix sum (compaction)
+    gmg_start *d_compact = nullptr;      // the used slots back to back: what leaves the GPU (grown on demand)
+    size_t compact_cap = 0;
+    uint64_t n = 0, max_starts = 0;
+    uint64_t n_packed = 0;       // starts of the last gmg_score_orfs_begin, back to back in d_compact
+    int scored = 0;
+    const gmg_reads *reads = nullptr;    // the batch the ORFs were validated against (gmg_orfs_upload): gmg_score_orfs takes no other
+    uint64_t reads_total = 0;
+    GmgScratch own{GmgScratch::NONE, nullptr, GmgScratch::DRIVER};
+    ~gmg_orf_batch() { gmg_segments_free(segs); }
 };
 
 struct OrfScanArgs {
@@ -1037,40 +1037,31 @@ extern "C" int gmg_orfs_upload(const gmg_reads *reads, const gmg_orf *orfs, uint
     if (start_off[n] > (uint64_t)gmg_opt(GMG_OPT_MG_MAX_ENTRIES) || n > (uint64_t)gmg_opt(GMG_OPT_MG_MAX_ENTRIES))
         return gmg_set_error(GMG_ETOOBIG, "gmg_orfs_upload: %llu ORFs with room for %llu starts, gmg_orf_result.start_begin holds %lld: split the batch",
                              (unsigned long long)n, (unsigned long long)start_off[n], gmg_opt(GMG_OPT_MG_MAX_ENTRIES));
-    gmg_orf_batch *b = new (std::nothrow) gmg_orf_batch();
+    std::unique_ptr<gmg_orf_batch> b(new (std::nothrow) gmg_orf_batch());
     if (!b) return gmg_set_error(GMG_ENOMEM, "gmg_orfs_upload: out of host memory");
-    memset(b, 0, sizeof *b);
     b->n = n;
     b->max_starts = start_off[n];
     b->reads = reads;
     b->reads_total = reads->total_bases;
     int rc = gmg_segments_upload(reads, segs.data(), n, nullptr, nullptr, &b->segs);
-    if (rc) { delete b; return rc; }
-    hipError_t e = hipMalloc((void **)&b->d_orfs, (n ? n : 1) * sizeof(gmg_orf));
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_start_off, (n + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_results, (n ? n : 1) * sizeof(gmg_orf_result));
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_starts, (b->max_starts ? b->max_starts : 1) * sizeof(gmg_start));
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_nst, (n + 1) * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_coff, (n + 1) * 4);
-    if (e == hipSuccess) e = hipMemset(b->d_nst, 0, (n + 1) * 4);
-    b->d_scan_tmp = nullptr;
-    b->scan_tmp_bytes = 0;
-    if (e == hipSuccess && n) e = hipMemcpy(b->d_orfs, orfs, n * sizeof(gmg_orf), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(b->d_start_off, start_off.data(), (n + 1) * 8, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { gmg_orf_batch_free(b); return gmg_set_error(GMG_ENOMEM, "gmg_orfs_upload: %s", hipGetErrorString(e)); }
+    if (rc) return rc;
+    GMG_HIP(b->own.alloc(&b->d_orfs, (n ? n : 1) * sizeof(gmg_orf)));
+    GMG_HIP(b->own.alloc(&b->d_start_off, (n + 1) * 8));
+    GMG_HIP(b->own.alloc(&b->d_results, (n ? n : 1) * sizeof(gmg_orf_result)));
+    GMG_HIP(b->own.alloc(&b->d_starts, (b->max_starts ? b->max_starts : 1) * sizeof(gmg_start)));
+    GMG_HIP(b->own.alloc(&b->d_nst, (n + 1) * 4));
+    GMG_HIP(b->own.alloc(&b->d_coff, (n + 1) * 4));
+    GMG_HIP(hipMemset(b->d_nst, 0, (n + 1) * 4));
+    if (n) GMG_HIP(hipMemcpy(b->d_orfs, orfs, n * sizeof(gmg_orf), hipMemcpyHostToDevice));
+    GMG_HIP(hipMemcpy(b->d_start_off, start_off.data(), (n + 1) * 8, hipMemcpyHostToDevice));
     if (out_max_starts) *out_max_starts = b->max_starts;
-    *out = b;
+    *out = b.release();
     return GMG_OK;
 }
 
 extern "C" int gmg_orf_batch_free(gmg_orf_batch *b)
 {
     if (!b) return GMG_OK;
-    if (b->segs) gmg_segments_free(b->segs);
-    void *ptrs[] = {b->d_orfs, b->d_start_off, b->d_score, b->d_indep, b->d_results, b->d_starts, b->d_gene6, b->d_tmp, b->d_walk, b->d_heads, b->d_qpre, b->d_qneed,
-                    b->d_nst, b->d_coff, b->d_scan_tmp, b->d_compact};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
     delete b;
     return GMG_OK;
 }
@@ -1098,16 +1089,6 @@ extern "C" int gmg_score_orfs_fetch(const gmg_orf_batch *b, gmg_orf_result *resu
     return GMG_OK;
 }
 
-// The batch's scratch comes on first use: a missing array is allocated straight into its field.  A batch that holds only some of
-// them is harmless: every array is tested on its own, and gmg_orf_batch_free frees whatever is there.
-template <class T> static hipError_t orf_lazy(T *&field, size_t bytes)
-{
-    if (field) return hipSuccess;
-    const hipError_t e = hipMalloc((void **)&field, bytes);
-    if (e != hipSuccess) field = nullptr;
-    return e;
-}
-
 extern "C" int gmg_score_orfs_begin(const gmg_model *gene, const gmg_model *nul, const gmg_reads *reads,
                                     const gmg_orf_batch *b, const gmg_orf_params *prm, uint64_t *out_n_starts, void *stream)
 {
@@ -1125,6 +1106,12 @@ extern "C" int gmg_score_orfs_begin(const gmg_model *gene, const gmg_model *nul,
     if (b->n == 0) return GMG_OK;
     hipStream_t s = (hipStream_t)stream;
     gmg_orf_batch *mb = const_cast<gmg_orf_batch *>(b);            // scratch is allocated on first use
+    // ... every array tested on its own; one that is there has the size the batch's reads and ORFs give it, which do not change
+    auto first_use = [mb](auto *&field, size_t bytes) {
+        const size_t count = bytes / sizeof *field;    // (every size below is a whole number of items)
+        size_t cap = field ? count : 0;
+        return mb->own.regrow(field, cap, count);
+    };
     // option orfs_exact_path: 0 = the fastest path the models allow, 1 = the any-shape path, 2 = k_orf_fused even where the events path could run
     const bool fused = gmg_f6_shape(gene->dev) && gene->dev.P == 3 && nul->dev.has_dense && nul->dev.W == 3 && nul->dev.P == 3 && gmg_opt(GMG_OPT_ORFS_EXACT_PATH) != 1;
     // the events path: every sum of the batch exact in any order (the test of gmg_mg.hip's fused kernel; R = longest read + 2)
@@ -1139,12 +1126,12 @@ extern "C" int gmg_score_orfs_begin(const gmg_model *gene, const gmg_model *nul,
     if (events) {
         const uint64_t head_words = reads->total_bases / 32 + 4;
         const uint64_t meta_stride = reads->total_bases / 8 + reads->n_reads + 64;
-        GMG_HIP(orf_lazy(mb->d_qpre, (size_t)2 * meta_stride * 2));
-        GMG_HIP(orf_lazy(mb->d_qneed, (size_t)2 * meta_stride));
+        GMG_HIP(first_use(mb->d_qpre, (size_t)2 * meta_stride * 2));
+        GMG_HIP(first_use(mb->d_qneed, (size_t)2 * meta_stride));
         // (eight spare entries: k_orf_walk_sums8 / 8p load a lane's eight values of every row without a predicate, up to entry 5 total + 7)
-        GMG_HIP(orf_lazy(mb->d_gene6, ((size_t)6 * reads->total_bases + 8) * sizeof(float)));
-        GMG_HIP(orf_lazy(mb->d_walk, ((size_t)2 * reads->total_bases + 8) * sizeof(double)));
-        GMG_HIP(orf_lazy(mb->d_heads, (size_t)2 * head_words * 4));
+        GMG_HIP(first_use(mb->d_gene6, ((size_t)6 * reads->total_bases + 8) * sizeof(float)));
+        GMG_HIP(first_use(mb->d_walk, ((size_t)2 * reads->total_bases + 8) * sizeof(double)));
+        GMG_HIP(first_use(mb->d_heads, (size_t)2 * head_words * 4));
         int rc = gmg_launch_gene6(gene, reads, mb->d_gene6, s);
         if (rc) return gmg_set_error(rc, "gmg_score_orfs: gene-only pass refused the model");
         OrfWalkArgs wa;
@@ -1188,14 +1175,14 @@ extern "C" int gmg_score_orfs_begin(const gmg_model *gene, const gmg_model *nul,
         else hipLaunchKernelGGL(k_orf_walk_sums, dim3((unsigned)(wblocks < 256 * 64 ? wblocks : 256 * 64)), dim3(256), 0, s, wa);
         GMG_HIP(hipGetLastError());
     } else if (fused) {
-        GMG_HIP(orf_lazy(mb->d_gene6, ((size_t)6 * reads->total_bases + 8) * sizeof(float)));
-        GMG_HIP(orf_lazy(mb->d_tmp, (b->max_starts ? b->max_starts : 1) * sizeof(OrfTmp)));
+        GMG_HIP(first_use(mb->d_gene6, ((size_t)6 * reads->total_bases + 8) * sizeof(float)));
+        GMG_HIP(first_use(mb->d_tmp, (b->max_starts ? b->max_starts : 1) * sizeof(OrfTmp)));
         int rc = gmg_launch_gene6(gene, reads, mb->d_gene6, s);
         if (rc) return gmg_set_error(rc, "gmg_score_orfs: gene-only pass refused the model");
     } else {
         const size_t tl = b->segs->total_len;
-        GMG_HIP(orf_lazy(mb->d_score, (tl ? tl : 1) * 8));
-        GMG_HIP(orf_lazy(mb->d_indep, (tl ? tl : 1) * 8));
+        GMG_HIP(first_use(mb->d_score, (tl ? tl : 1) * 8));
+        GMG_HIP(first_use(mb->d_indep, (tl ? tl : 1) * 8));
         int rc = gmg_launch_seg_cum(gene, reads, b->segs, gene->dev.P == 1 ? 0 : 1, b->d_score, nullptr, s);
         if (rc) return rc;
         rc = gmg_launch_seg_cum(nul, reads, b->segs, nul->dev.P == 1 ? 0 : 1, b->d_indep, nullptr, s);
@@ -1262,14 +1249,9 @@ extern "C" int gmg_score_orfs_begin(const gmg_model *gene, const gmg_model *nul,
     GMG_HIP(hipStreamSynchronize(s));
     if (total > b->max_starts) return gmg_set_error(GMG_EHIP, "gmg_score_orfs: %u starts in %llu slots", total,
                                                     (unsigned long long)b->max_starts);
-    if (total > b->compact_cap) {
-        if (mb->d_compact) (void)hipFree(mb->d_compact);
-        mb->d_compact = nullptr;
+    if (total > b->compact_cap) {                       // (replaced with some room: the next call's lists are about as long)
         mb->compact_cap = 0;
-        const uint64_t cap = (uint64_t)total + total / 8 + 1024;
-        hipError_t e = hipMalloc((void **)&mb->d_compact, cap * sizeof(gmg_start));
-        if (e != hipSuccess) return gmg_set_error(GMG_ENOMEM, "gmg_score_orfs: start lists: %s", hipGetErrorString(e));
-        mb->compact_cap = cap;
+        GMG_HIP(mb->own.regrow(mb->d_compact, mb->compact_cap, (size_t)total + total / 8 + 1024));
     }
     hipLaunchKernelGGL(k_orf_compact, dim3(grid), dim3(256), 0, s, b->d_starts, b->d_start_off, b->d_coff, b->d_results,
                        b->d_compact, b->n);

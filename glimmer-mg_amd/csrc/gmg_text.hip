@@ -33,14 +33,20 @@ struct TxRec {
     uint32_t nlet;               // letters (< 2^31); TX_REV: reverse strand
 };
 
-struct gmg_letters {
-    uint8_t *d_letters;
+struct GMG_HIDDEN gmg_letters {
+    uint8_t *d_letters = nullptr;
     std::vector<uint64_t> off;   // n_reads + 1 (host)
-    uint64_t n_reads;
-    char *d_text;                // the text of the last call
-    size_t cap_text;
-    hipEvent_t ev[2];            // around the last call's kernel
-    int timed;                   // ... which there was
+    uint64_t n_reads = 0;
+    char *d_text = nullptr;      // the text of the last call
+    size_t cap_text = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};   // around the last call's kernel
+    int timed = 0;               // ... which there was
+    GmgScratch own{GmgScratch::DEVICE, nullptr};         // (the last call's kernel may still run when the handle goes)
+    ~gmg_letters()
+    {
+        if (ev[0]) (void)hipEventDestroy(ev[0]);
+        if (ev[1]) (void)hipEventDestroy(ev[1]);
+    }
 };
 
 // the largest k in [lo, hi] with off[k] <= g (off[lo] <= g)
@@ -167,39 +173,21 @@ extern "C" int gmg_letters_upload(const char *letters, const uint64_t *base_offs
         if (base_offsets[r + 1] < base_offsets[r]) return gmg_set_error(GMG_EINVAL, "gmg_letters_upload: the offsets descend at read %llu", (unsigned long long)r);
     const uint64_t total = base_offsets[n_reads];
     if (!letters && total) return gmg_set_error(GMG_EINVAL, "gmg_letters_upload: NULL letters");
-    GmgScratch sc;
-    uint8_t *d = nullptr;
-    GMG_HIP(sc.alloc(&d, total ? total : 1));
-    if (total) GMG_HIP(hipMemcpy(d, letters, total, hipMemcpyHostToDevice));
-    gmg_letters *l = new (std::nothrow) gmg_letters();
+    std::unique_ptr<gmg_letters> l(new (std::nothrow) gmg_letters());
     if (!l) return gmg_set_error(GMG_ENOMEM, "gmg_letters_upload: out of host memory");
-    l->ev[0] = l->ev[1] = nullptr;
-    hipError_t e = hipEventCreate(&l->ev[0]);
-    if (e == hipSuccess) e = hipEventCreate(&l->ev[1]);
-    if (e != hipSuccess) {
-        if (l->ev[0]) (void)hipEventDestroy(l->ev[0]);
-        delete l;
-        return gmg_set_error(GMG_EHIP, "gmg_letters_upload: hipEventCreate failed: %s", hipGetErrorString(e));
-    }
+    GMG_HIP(l->own.alloc(&l->d_letters, total ? total : 1));
+    if (total) GMG_HIP(hipMemcpy(l->d_letters, letters, total, hipMemcpyHostToDevice));
+    GMG_HIP(hipEventCreate(&l->ev[0]));
+    GMG_HIP(hipEventCreate(&l->ev[1]));
     l->off.assign(base_offsets, base_offsets + n_reads + 1);
     l->n_reads = n_reads;
-    l->d_letters = d;
-    l->d_text = nullptr;
-    l->cap_text = 0;
-    l->timed = 0;
-    sc.detach(d);
-    *out = l;
+    *out = l.release();
     return GMG_OK;
 }
 
 extern "C" int gmg_letters_free(gmg_letters *l)
 {
     if (!l) return GMG_OK;
-    (void)hipDeviceSynchronize();
-    gmg_pool_release(l->d_letters);
-    if (l->d_text) gmg_pool_release(l->d_text);
-    (void)hipEventDestroy(l->ev[0]);
-    (void)hipEventDestroy(l->ev[1]);
     delete l;
     return GMG_OK;
 }
@@ -266,14 +254,8 @@ static int text_run(const char *who, gmg_letters *l, const gmg_gene_region *regi
     }
     *bytes = (size_t)total;
     if (total == 0) return GMG_OK;
-    if (l->cap_text < total) {                           // (whole 16-byte pieces: the block cache hands out 256-byte aligned blocks)
-        if (l->d_text) { gmg_pool_release_after(l->d_text, s); l->d_text = nullptr; l->cap_text = 0; }
-        const size_t want = (size_t)((total + 255) & ~255ull);
-        void *p = nullptr;
-        GMG_HIP(gmg_pool_alloc(&p, want));
-        l->d_text = (char *)p;
-        l->cap_text = want;
-    }
+    // (whole 16-byte pieces: the block cache hands out 256-byte aligned blocks; an earlier text goes back once s has come this far)
+    if (l->cap_text < total) GMG_HIP(l->own.regrow(l->d_text, l->cap_text, (size_t)((total + 255) & ~255ull), &s));
     TxRec *d_rec = nullptr;
     uint64_t *d_toff = nullptr;
     uint8_t *d_heads = nullptr, *d_tab = nullptr;

@@ -27,21 +27,20 @@
 // |x| * 1e4 below 2^52: the product's rounding error analysis of th_key holds (ulp <= 1/2), and a key fits an int64 easily
 #define TH_LIMIT 4503599627370496.0
 
-struct gmg_tophits {
-    const gmg_reads *reads;      // the caller's batch (gmg_tophits_scores scores it; it must outlive the handle)
-    uint64_t n_reads;
-    int top_hits;
-    int64_t *d_keys;             // [top_hits][n_reads] slot-major (a lane's loads of one slot are coalesced across the wave)
-    int32_t *d_models;           // [top_hits][n_reads], -1 = empty slot
-    uint32_t *d_flag;            // set by a kernel that met a value it cannot key (NaN, infinite, |x| >= 2^52 / 1e4)
-    uint8_t *d_inf;              // [cap_inf] the batch's informative flags
-    int cap_inf;
-    double *d_sums;              // [cap_sums] gmg_tophits_scores' scratch: [B][n_reads][2]
-    size_t cap_sums;
-    uint32_t *d_len;             // [cap_items] field lengths of gmg_tophits_format_rows
-    uint64_t *d_off;             // [cap_off] their exclusive sums
-    char *d_text;                // [cap_text]
-    size_t cap_items, cap_off, cap_text;
+struct GMG_HIDDEN gmg_tophits {
+    const gmg_reads *reads = nullptr;    // the caller's batch (gmg_tophits_scores scores it; it must outlive the handle)
+    uint64_t n_reads = 0;
+    int top_hits = 0;
+    int64_t *d_keys = nullptr;   // [top_hits][n_reads] slot-major (a lane's loads of one slot are coalesced across the wave)
+    int32_t *d_models = nullptr; // [top_hits][n_reads], -1 = empty slot
+    uint32_t *d_flag = nullptr;  // set by a kernel that met a value it cannot key (NaN, infinite, |x| >= 2^52 / 1e4)
+    uint8_t *d_inf = nullptr;    // [cap_inf] the batch's informative flags
+    double *d_sums = nullptr;    // [cap_sums] gmg_tophits_scores' scratch: [B][n_reads][2]
+    uint32_t *d_len = nullptr;   // [cap_items] field lengths of gmg_tophits_format_rows
+    uint64_t *d_off = nullptr;   // [cap_off] their exclusive sums
+    char *d_text = nullptr;      // [cap_text]
+    size_t cap_inf = 0, cap_sums = 0, cap_items = 0, cap_off = 0, cap_text = 0;
+    GmgScratch own{GmgScratch::NONE, nullptr, GmgScratch::DRIVER};
 };
 
 // ---------------------------------------------------------------------------
@@ -190,18 +189,6 @@ unsigned grid_for(uint64_t items)
     return (unsigned)(b == 0 ? 1 : (b < 256 * 64 ? b : 256 * 64));
 }
 
-// a device buffer of at least `bytes`, replaced (not copied) when it is too small
-template <typename T>
-int grow(T **p, size_t *cap, size_t count, const char *who)
-{
-    if (*p && *cap >= count) return GMG_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    hipError_t e = hipMalloc((void **)p, (count ? count : 1) * sizeof(T));
-    if (e != hipSuccess) { *p = nullptr; return gmg_set_error(GMG_ENOMEM, "%s: %s", who, hipGetErrorString(e)); }
-    *cap = count;
-    return GMG_OK;
-}
-
 // the flag the kernels set for a value without a key: read back (the stream is synchronised) and cleared
 int check_flag(gmg_tophits *h, hipStream_t s, const char *who)
 {
@@ -224,33 +211,25 @@ extern "C" int gmg_tophits_create(const gmg_reads *reads, int top_hits, gmg_toph
     *out = nullptr;
     if (top_hits < 1 || top_hits > TH_MAX_HITS)
         return gmg_set_error(GMG_EINVAL, "gmg_tophits_create: top_hits %d outside 1..%d", top_hits, TH_MAX_HITS);
-    gmg_tophits *h = new (std::nothrow) gmg_tophits();
+    std::unique_ptr<gmg_tophits> h(new (std::nothrow) gmg_tophits());
     if (!h) return gmg_set_error(GMG_ENOMEM, "gmg_tophits_create: out of host memory");
-    memset(h, 0, sizeof *h);
     h->reads = reads;
     h->n_reads = reads->n_reads;
     h->top_hits = top_hits;
     const size_t slots = (size_t)top_hits * (h->n_reads ? h->n_reads : 1);
-    hipError_t e = hipMalloc((void **)&h->d_keys, slots * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_models, slots * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_flag, 4);
-    if (e == hipSuccess) e = hipMemset(h->d_keys, 0, slots * 8);
-    if (e == hipSuccess) e = hipMemset(h->d_models, 0xff, slots * 4);
-    if (e == hipSuccess) e = hipMemset(h->d_flag, 0, 4);
-    if (e != hipSuccess) {
-        gmg_tophits_free(h);
-        return gmg_set_error(GMG_ENOMEM, "gmg_tophits_create: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    GMG_HIP(h->own.alloc(&h->d_keys, slots * 8));
+    GMG_HIP(h->own.alloc(&h->d_models, slots * 4));
+    GMG_HIP(h->own.alloc(&h->d_flag, 4));
+    GMG_HIP(hipMemset(h->d_keys, 0, slots * 8));
+    GMG_HIP(hipMemset(h->d_models, 0xff, slots * 4));
+    GMG_HIP(hipMemset(h->d_flag, 0, 4));
+    *out = h.release();
     return GMG_OK;
 }
 
 extern "C" int gmg_tophits_free(gmg_tophits *h)
 {
     if (!h) return GMG_OK;
-    void *bufs[] = {h->d_keys, h->d_models, h->d_flag, h->d_inf, h->d_sums, h->d_len, h->d_off, h->d_text};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
     delete h;
     return GMG_OK;
 }
@@ -266,10 +245,7 @@ extern "C" int gmg_tophits_update_sums(gmg_tophits *h, const double *d_sums, int
     if (B == 0 || h->n_reads == 0) return GMG_OK;
     const uint8_t *d_inf = nullptr;
     if (informative) {
-        size_t cap = (size_t)h->cap_inf;
-        int rc = grow(&h->d_inf, &cap, (size_t)B, "gmg_tophits_update_sums");
-        if (rc) return rc;
-        h->cap_inf = (int)cap;
+        GMG_HIP(h->own.regrow(h->d_inf, h->cap_inf, (size_t)B));
         GMG_HIP(hipMemcpyAsync(h->d_inf, informative, (size_t)B, hipMemcpyHostToDevice, s));
         d_inf = h->d_inf;
     }
@@ -286,9 +262,8 @@ extern "C" int gmg_tophits_scores(gmg_tophits *h, const gmg_model *const *models
     { int rc_enter = gmg_enter("gmg_tophits_scores"); if (rc_enter) return rc_enter; }
     if (!h || B < 0 || (!models && B)) return gmg_set_error(GMG_EINVAL, "gmg_tophits_scores: NULL argument");
     if (d_sums_out) *d_sums_out = nullptr;
-    int rc = grow(&h->d_sums, &h->cap_sums, (size_t)B * h->n_reads * 2, "gmg_tophits_scores");
-    if (rc) return rc;
-    rc = gmg_score_reads_strings(models, B, h->reads, h->d_sums, stream);
+    GMG_HIP(h->own.regrow(h->d_sums, h->cap_sums, (size_t)B * h->n_reads * 2));
+    int rc = gmg_score_reads_strings(models, B, h->reads, h->d_sums, stream);
     if (rc) return rc;
     rc = gmg_tophits_update_sums(h, h->d_sums, B, first_model, informative, forward_only, stream);
     if (rc == GMG_OK && d_sums_out) *d_sums_out = h->d_sums;
@@ -327,10 +302,8 @@ extern "C" int gmg_tophits_format_rows(gmg_tophits *h, const double *d_sums, int
         *bytes = need;
         return GMG_OK;
     }
-    int rc = grow(&h->d_len, &h->cap_items, n_items, "gmg_tophits_format_rows");
-    if (rc) return rc;
-    rc = grow(&h->d_off, &h->cap_off, n_items + 1, "gmg_tophits_format_rows");
-    if (rc) return rc;
+    GMG_HIP(h->own.regrow(h->d_len, h->cap_items, n_items));
+    GMG_HIP(h->own.regrow(h->d_off, h->cap_off, n_items + 1));
     hipLaunchKernelGGL(k_th_len, dim3(grid_for(n_items)), dim3(TH_BLOCK), 0, s, (const double2 *)d_sums, n_items, forward_only, h->d_len,
                        h->d_flag);
     GMG_HIP(hipGetLastError());
@@ -339,7 +312,7 @@ extern "C" int gmg_tophits_format_rows(gmg_tophits *h, const double *d_sums, int
     GMG_HIP(hipMemcpyAsync(&tail[0], h->d_off + n_items - 1, 8, hipMemcpyDeviceToHost, s));
     uint32_t last = 0;
     GMG_HIP(hipMemcpyAsync(&last, h->d_len + n_items - 1, 4, hipMemcpyDeviceToHost, s));
-    rc = check_flag(h, s, "gmg_tophits_format_rows");   // (synchronises)
+    int rc = check_flag(h, s, "gmg_tophits_format_rows");   // (synchronises)
     if (rc) return rc;
     tail[1] = last;
     const size_t need = (size_t)(tail[0] + tail[1]);
@@ -349,8 +322,7 @@ extern "C" int gmg_tophits_format_rows(gmg_tophits *h, const double *d_sums, int
         *bytes = need;
         return rc;
     }
-    rc = grow(&h->d_text, &h->cap_text, need, "gmg_tophits_format_rows");
-    if (rc) return rc;
+    GMG_HIP(h->own.regrow(h->d_text, h->cap_text, need));
     hipLaunchKernelGGL(k_th_text, dim3(grid_for(n_items)), dim3(TH_BLOCK), 0, s, (const double2 *)d_sums, nr, n_items, forward_only,
                        (const uint64_t *)h->d_off, h->d_text);
     GMG_HIP(hipGetLastError());

@@ -37,18 +37,20 @@
 #include <stdio.h>
 #include <vector>
 
-struct gmg_trainer {
-    const gmg_reads *strings;   // borrowed: must outlive the trainer
-    int W, D, P;
-    int next_level;             // levels are taken in order
-    int32_t *d_node;            // [total_bases] node reached by the window starting at that base, -1 = none / stopped
-    int8_t *d_mip_prev;         // [P][4^(level-1)] mut_info_pos of the level above the one being counted
-    int32_t *d_cnt;             // [P][4^level][max(W-1,1)][16] of the level being counted
-    size_t cnt_cap;             // counters allocated at d_cnt
+struct GMG_HIDDEN gmg_trainer {
+    const gmg_reads *strings = nullptr;  // borrowed: must outlive the trainer
+    int W = 0, D = 0, P = 0;
+    int next_level = 0;         // levels are taken in order
+    int32_t *d_node = nullptr;  // [total_bases] node reached by the window starting at that base, -1 = none / stopped
+    int8_t *d_mip_prev = nullptr;        // [P][4^(level-1)] mut_info_pos of the level above the one being counted
+    int32_t *d_cnt = nullptr;   // [P][4^level][max(W-1,1)][16] of the level being counted
+    size_t cnt_cap = 0;         // counters allocated at d_cnt
     // the sorted path (allocated on first use): (table, window) pairs before / after the sort + hipcub's scratch
-    uint32_t *d_key, *d_key_sorted, *d_win, *d_win_sorted;
-    void *d_sort_tmp;
-    size_t sort_tmp_bytes;
+    uint32_t *d_key = nullptr, *d_key_sorted = nullptr, *d_win = nullptr, *d_win_sorted = nullptr;
+    size_t key_cap = 0;         // items at each of the four
+    unsigned char *d_sort_tmp = nullptr;
+    size_t sort_tmp_bytes = 0;
+    GmgScratch own{GmgScratch::DEVICE, nullptr};         // (kernels of the last level may still run when the trainer goes)
 };
 
 namespace {
@@ -225,47 +227,27 @@ extern "C" int gmg_trainer_create(const gmg_reads *strings, int model_len, int m
             return gmg_set_error(GMG_EBADMODEL, "gmg_trainer_create: %.0f counters on level %d (model_len %d, periodicity %d); "
                                  "at most 2^31 - 1", counters, model_depth, model_len, periodicity);
     }
-    gmg_trainer *t = new (std::nothrow) gmg_trainer();
+    std::unique_ptr<gmg_trainer> t(new (std::nothrow) gmg_trainer());
     if (!t) return gmg_set_error(GMG_ENOMEM, "gmg_trainer_create: out of host memory");
     t->strings = strings;
     t->W = model_len;
     t->D = model_depth;
     t->P = periodicity;
-    t->next_level = 0;
-    t->d_node = nullptr;
-    t->d_mip_prev = nullptr;
-    t->d_cnt = nullptr;
-    t->d_key = t->d_key_sorted = t->d_win = t->d_win_sorted = nullptr;
-    t->d_sort_tmp = nullptr;
-    t->sort_tmp_bytes = 0;
     const int npos = model_len > 1 ? model_len - 1 : 1;
     const size_t on_last = (size_t)(level_first(model_depth + 1) - level_first(model_depth));
     t->cnt_cap = (size_t)periodicity * on_last * npos * 16;
     const size_t prev_cap = (size_t)periodicity * (model_depth > 0 ? on_last / 4 : 1);
     // from the library's cache of device blocks: a training run per genome asks for the same sizes again and again
-    hipError_t e = gmg_pool_alloc((void **)&t->d_node, (strings->total_bases + 1) * sizeof(int32_t));
-    if (e == hipSuccess) e = gmg_pool_alloc((void **)&t->d_mip_prev, prev_cap);
-    if (e == hipSuccess) e = gmg_pool_alloc((void **)&t->d_cnt, t->cnt_cap * sizeof(int32_t));
-    if (e != hipSuccess) {
-        gmg_trainer_free(t);
-        return gmg_set_error(GMG_ENOMEM, "gmg_trainer_create: device allocation failed: %s", hipGetErrorString(e));
-    }
-    *out = t;
+    GMG_HIP(t->own.alloc(&t->d_node, (strings->total_bases + 1) * sizeof(int32_t)));
+    GMG_HIP(t->own.alloc(&t->d_mip_prev, prev_cap));
+    GMG_HIP(t->own.alloc(&t->d_cnt, t->cnt_cap * sizeof(int32_t)));
+    *out = t.release();
     return GMG_OK;
 }
 
 extern "C" int gmg_trainer_free(gmg_trainer *t)
 {
     if (!t) return GMG_OK;
-    (void)hipDeviceSynchronize();
-    if (t->d_node) gmg_pool_release(t->d_node);
-    if (t->d_mip_prev) gmg_pool_release(t->d_mip_prev);
-    if (t->d_cnt) gmg_pool_release(t->d_cnt);
-    gmg_pool_release(t->d_key);
-    gmg_pool_release(t->d_key_sorted);
-    gmg_pool_release(t->d_win);
-    gmg_pool_release(t->d_win_sorted);
-    gmg_pool_release(t->d_sort_tmp);
     delete t;
     return GMG_OK;
 }
@@ -328,25 +310,14 @@ extern "C" int gmg_trainer_level_counts(gmg_trainer *t, int level, const int16_t
             const uint32_t n_tables = (uint32_t)(t->P * a.on_level);
             int end_bit = 1;
             while (end_bit < 32 && (1ull << end_bit) <= n_tables) end_bit++;     // the keys go up to n_tables (= no table)
-            if (!t->d_key) {
-                hipError_t e = gmg_pool_alloc((void **)&t->d_key, n * sizeof(uint32_t));
-                if (e == hipSuccess) e = gmg_pool_alloc((void **)&t->d_key_sorted, n * sizeof(uint32_t));
-                if (e == hipSuccess) e = gmg_pool_alloc((void **)&t->d_win, n * sizeof(uint32_t));
-                if (e == hipSuccess) e = gmg_pool_alloc((void **)&t->d_win_sorted, n * sizeof(uint32_t));
-                if (e != hipSuccess)
-                    return gmg_set_error(GMG_ENOMEM, "gmg_trainer_level_counts: device allocation failed: %s", hipGetErrorString(e));
-            }
+            GMG_HIP(t->own.regrow(t->d_key, t->key_cap, n));       // (first use: n is the set's size at every level)
+            GMG_HIP(t->own.regrow(t->d_key_sorted, t->key_cap, n));
+            GMG_HIP(t->own.regrow(t->d_win, t->key_cap, n));
+            GMG_HIP(t->own.regrow(t->d_win_sorted, t->key_cap, n));
             size_t need = 0;
             GMG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need, t->d_key, t->d_key_sorted, t->d_win, t->d_win_sorted,
                                                        (int)n, 0, end_bit, (hipStream_t)0));
-            if (need > t->sort_tmp_bytes) {
-                gmg_pool_release(t->d_sort_tmp);
-                t->d_sort_tmp = nullptr;
-                t->sort_tmp_bytes = 0;
-                if (gmg_pool_alloc(&t->d_sort_tmp, need) != hipSuccess)
-                    return gmg_set_error(GMG_ENOMEM, "gmg_trainer_level_counts: device allocation failed (sort scratch)");
-                t->sort_tmp_bytes = need;
-            }
+            GMG_HIP(t->own.regrow(t->d_sort_tmp, t->sort_tmp_bytes, need));
             a.key = t->d_key;
             a.win = t->d_win;
             const unsigned grid = (unsigned)(a.n_tiles < 8192 ? a.n_tiles : 8192);

@@ -34,18 +34,22 @@
 #define WN_BLOCK 256
 #define WN_GRID_CAP (256 * 32)
 
-struct gmg_windows {
-    uint64_t *d_off;                     // n_reads + 1
-    int32_t *d_counts;                   // [n_windows][5]
-    uint64_t n_reads, n_windows;
+struct GMG_HIDDEN gmg_windows {
+    uint64_t *d_off = nullptr;           // n_reads + 1
+    int32_t *d_counts = nullptr;         // [n_windows][5]
+    uint64_t n_reads = 0, n_windows = 0;
     hipStream_t s;
+    GmgScratch own;                      // the blocks are free once what is queued on s when the handle goes has run
+    explicit gmg_windows(hipStream_t stream) : s(stream), own(GmgScratch::AFTER, stream) {}
 };
 
-struct gmg_gaps {
-    gmg_gene_region *d_gaps;
-    uint64_t *d_off;                     // n_reads + 1
-    uint64_t n_reads, n_gaps;
+struct GMG_HIDDEN gmg_gaps {
+    gmg_gene_region *d_gaps = nullptr;
+    uint64_t *d_off = nullptr;           // n_reads + 1
+    uint64_t n_reads = 0, n_gaps = 0;
     hipStream_t s;
+    GmgScratch own;                      // (as gmg_windows)
+    explicit gmg_gaps(hipStream_t stream) : s(stream), own(GmgScratch::AFTER, stream) {}
 };
 
 // c, g, t among the 2-bit fields of w
@@ -262,14 +266,12 @@ extern "C" int gmg_window_counts(const gmg_reads *reads, int64_t window_len, int
                            (const uint64_t *)d_amb, n_amb, (const uint32_t *)d_a[0], (const uint32_t *)d_a[1], (const uint32_t *)d_a[2], d_counts);
         GMG_HIP(hipGetLastError());
     }
-    gmg_windows *res = new (std::nothrow) gmg_windows();
+    gmg_windows *res = new (std::nothrow) gmg_windows(s);
     if (!res) return gmg_set_error(GMG_ENOMEM, "gmg_window_counts: out of host memory");
-    res->d_off = d_row_off;
-    res->d_counts = d_counts;
+    res->d_off = res->own.take(sc, d_row_off);
+    res->d_counts = res->own.take(sc, d_counts);
     res->n_reads = n_reads;
     res->n_windows = total;
-    res->s = s;
-    sc.detach(d_row_off); sc.detach(d_counts);
     *out = res;
     return GMG_OK;
 }
@@ -303,8 +305,6 @@ extern "C" int gmg_windows_device(const gmg_windows *w, const uint64_t **d_read_
 extern "C" int gmg_windows_free(gmg_windows *w)
 {
     if (!w) return GMG_OK;
-    gmg_pool_release_after(w->d_off, w->s);
-    gmg_pool_release_after(w->d_counts, w->s);
     delete w;
     return GMG_OK;
 }
@@ -476,14 +476,12 @@ extern "C" int gmg_regions_uncovered(const gmg_reads *reads, const gmg_interval 
     hipLaunchKernelGGL(k_gap_items<true>, dim3(gmg_grid(n_items + 1, WN_BLOCK, WN_GRID_CAP)), dim3(WN_BLOCK), 0, s, (const uint64_t *)d_key2, (const uint64_t *)d_run, n,
                        reads->d_off, n_reads, min_len, (uint32_t *)nullptr, (const uint64_t *)d_slot, total, d_gaps, d_gap_off);
     GMG_HIP(hipGetLastError());
-    gmg_gaps *res = new (std::nothrow) gmg_gaps();
+    gmg_gaps *res = new (std::nothrow) gmg_gaps(s);
     if (!res) return gmg_set_error(GMG_ENOMEM, "gmg_regions_uncovered: out of host memory");
-    res->d_gaps = d_gaps;
-    res->d_off = d_gap_off;
+    res->d_gaps = res->own.take(sc, d_gaps);
+    res->d_off = res->own.take(sc, d_gap_off);
     res->n_reads = n_reads;
     res->n_gaps = total;
-    res->s = s;
-    sc.detach(d_gaps); sc.detach(d_gap_off);
     *out = res;
     return GMG_OK;
 }
@@ -508,8 +506,6 @@ extern "C" int gmg_gaps_fetch(const gmg_gaps *g, gmg_gene_region *gaps, uint64_t
 extern "C" int gmg_gaps_free(gmg_gaps *g)
 {
     if (!g) return GMG_OK;
-    gmg_pool_release_after(g->d_gaps, g->s);
-    gmg_pool_release_after(g->d_off, g->s);
     delete g;
     return GMG_OK;
 }

@@ -632,6 +632,9 @@ int gmg_mg_result_free(gmg_mg_result *r);
 /* gmg_mg_* keeps released device buffers for the next call (allocation of GB-sized buffers is slow);
  * this returns the idle ones to the driver. */
 int gmg_trim_cache(void);
+/* tests, debugging: the device blocks that the library's handles hold straight from hipMalloc, not from that cache (models, null
+ * sets, gmg_single, ORF batches, top hits, fixed models) -- a process-wide count; a handle that is freed holds none. */
+int gmg_debug_owned_blocks(uint64_t *out);
 
 /* ---- FASTA ingest on the device -----------------------------------------------------
  * Replaces the loop  while (Fasta_Read (fp, seq, hdr))  (src/Common/fasta.cc:236-286) + the per-base

@@ -31,6 +31,17 @@ def test_library_exports_every_declared_symbol(gmg):
     assert b"gfx950" in gmg.capi.lib().gmg_version()
 
 
+def test_debug_owned_blocks_is_declared_and_bound(gmg):
+    """the leak tests' counter of hipMalloc'd blocks in handles (tests/test_gpu_cache_accounting.py): include/gmg.h declares it,
+    capi.py binds it with the header's signature, and it answers without a device (a count, never negative: other tests' handles may live)"""
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gmg.h")).read(), flags=re.S)
+    assert re.search(r"\bint\s+gmg_debug_owned_blocks\s*\(\s*uint64_t\s*\*\s*out\s*\)\s*;", text)
+    assert gmg.capi.PROTOTYPES["gmg_debug_owned_blocks"] == (C.c_int, [C.POINTER(C.c_uint64)])
+    out = C.c_uint64(1 << 63)
+    assert gmg.capi.lib().gmg_debug_owned_blocks(C.byref(out)) == 0 and out.value < 1 << 32
+    assert gmg.capi.lib().gmg_debug_owned_blocks(None) == -1
+
+
 def test_base_code_matches_filter_subscript(gmg, oracle):
     lib = gmg.capi.lib()
     for ch in range(1, 128):
