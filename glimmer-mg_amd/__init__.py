@@ -15,4 +15,5 @@ from .api import (ModelSet, icm_bytes_info, model_info, model_blob, model_value_
                   fasta_ambiguous, extract_plan, edits_plan, RUN_UP, RUN_DOWN, RUN_SUB_UP, RUN_SUB_DOWN, RUN_LITERAL, RUN_LITERAL_AS_IS, icm_train_reads, EXTRACT_REVERSED, COORD_USE_DIR, COORD_NOWRAP, COORD_SKIP_START, COORD_SKIP_STOP, COORD_MULTI,
                   fasta_not_upper_acgt, FeatureTable, features_format, features_count, FEATURES_BLOCK, FEATURES_LENGTHS, FEATURES_STARTS, FEATURES_ORIENTS,
                   FEATURES_DIST, AUDIT_NEXT_STOP, GENE_AUDIT_DTYPE, audit_params, genes_audit,
-                  window_counts, regions_uncovered, uncovered_plan, Letters, text_params, memcpy_d2h)
+                  window_counts, regions_uncovered, uncovered_plan, Letters, text_params, memcpy_d2h,
+                  runs_text_params, RUNS_TEXT_DNA, RUNS_TEXT_PROTEIN)

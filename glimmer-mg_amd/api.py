@@ -581,6 +581,26 @@ def text_params(width=60, fwd=None, rev=None):
     return p
 
 
+RUNS_TEXT_DNA, RUNS_TEXT_PROTEIN = 0, 1               # GMG_RUNS_TEXT_*
+
+
+def runs_text_params(mode=RUNS_TEXT_DNA, transl_table=0, width=0, **fields):
+    """gmg_runs_text_params_script (host): the rules extract_aa.py prints by, under the translation table given (0: the script's
+    own) -- unless fields replace them: up / down / sub_up / sub_down (256 bytes each), literal (4), aa (64), pad, unknown (a byte)"""
+    p = capi.RunsTextParams()
+    _ck(capi.lib().gmg_runs_text_params_script(C.byref(p), int(mode), int(transl_table)))
+    p.width = int(width)
+    for name, value in fields.items():
+        if name in ("pad", "unknown"):
+            setattr(p, name, value if isinstance(value, int) else ord(value))
+        else:
+            value = bytes(value)
+            field = getattr(capi.RunsTextParams, name)
+            assert len(value) == field.size
+            C.memmove(C.addressof(p) + field.offset, value, len(value))
+    return p
+
+
 class Letters:
     """gmg_letters: the sequence bytes of a batch in HBM, one per base, and the text of regions of them (gmg_regions_text)"""
 
@@ -634,6 +654,55 @@ class Letters:
         regions, n, blob, off = self._args(regions, heads)
         ptr, size = C.c_void_p(), C.c_size_t(0)
         _ck(capi.lib().gmg_regions_text_device(self.h, regions, n, blob, _ptr(off), C.byref(params), C.byref(ptr), C.byref(size), None))
+        return ptr, size.value
+
+    @staticmethod
+    def _run_args(runs, string_run_off, heads, pad_front, pad_behind):
+        """runs [(read, first, len, kind)] or a uint32 [n, 4] array; heads as for regions; pads: None (0) or one count per string"""
+        runs = np.ascontiguousarray(np.asarray(runs, np.uint32).reshape(-1, 4))
+        sro = np.ascontiguousarray(string_run_off, np.uint64)
+        n = len(sro) - 1
+        if isinstance(heads, tuple):
+            blob, off = bytes(heads[0]), np.ascontiguousarray(heads[1], np.uint64)
+        else:
+            assert len(heads) == n
+            blob = b"".join(heads)
+            off = np.zeros(n + 1, np.uint64)
+            off[1:] = np.cumsum([len(h) for h in heads], dtype=np.uint64)
+        pads = [None if p is None else np.ascontiguousarray(p, np.uint32) for p in (pad_front, pad_behind)]
+        assert all(p is None or len(p) == n for p in pads)
+        keep = (runs, sro, off, pads)                   # (the arrays the pointers point into)
+        return keep, (_ptr(runs) if len(runs) else None, len(runs), _ptr(sro), n, *[None if p is None or n == 0 else _ptr(p) for p in pads],
+                      blob, _ptr(off))
+
+    def runs_text_size(self, runs, string_run_off, heads, params, pad_front=None, pad_behind=None):
+        """gmg_runs_text with host_out = NULL: the length of the text"""
+        keep, args = self._run_args(runs, string_run_off, heads, pad_front, pad_behind)
+        size = C.c_size_t(0)
+        _ck(capi.lib().gmg_runs_text(self.h, *args, C.byref(params), None, C.byref(size), None))
+        return size.value
+
+    def runs_text(self, runs, string_run_off, heads, params, pad_front=None, pad_behind=None, capacity=None, out=None):
+        """gmg_runs_text -> the text (bytes): string k = pad_front[k] pad bytes, runs[string_run_off[k] : string_run_off[k + 1]],
+        pad_behind[k] pad bytes, or its translation (runs_text_params).  capacity / out as for regions_text"""
+        keep, args = self._run_args(runs, string_run_off, heads, pad_front, pad_behind)
+        if out is None:
+            if capacity is None:
+                size = C.c_size_t(0)
+                _ck(capi.lib().gmg_runs_text(self.h, *args, C.byref(params), None, C.byref(size), None))
+                capacity = size.value
+            buf = np.zeros(max(int(capacity), 1), np.uint8)
+        else:
+            buf, capacity = out, out.size
+        size = C.c_size_t(int(capacity))
+        _ck(capi.lib().gmg_runs_text(self.h, *args, C.byref(params), _ptr(buf), C.byref(size), None))
+        return size.value if out is not None else buf[:size.value].tobytes()
+
+    def runs_text_device(self, runs, string_run_off, heads, params, pad_front=None, pad_behind=None):
+        """gmg_runs_text_device -> (device pointer, bytes): the text stays in the handle's buffer until the next text call"""
+        keep, args = self._run_args(runs, string_run_off, heads, pad_front, pad_behind)
+        ptr, size = C.c_void_p(), C.c_size_t(0)
+        _ck(capi.lib().gmg_runs_text_device(self.h, *args, C.byref(params), C.byref(ptr), C.byref(size), None))
         return ptr, size.value
 
     def kernel_ms(self):

@@ -28,6 +28,12 @@ class TextParams(C.Structure):
     _fields_ = [("fwd", C.c_uint8 * 256), ("rev", C.c_uint8 * 256), ("width", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class RunsTextParams(C.Structure):
+    _fields_ = [("up", C.c_uint8 * 256), ("down", C.c_uint8 * 256), ("sub_up", C.c_uint8 * 256), ("sub_down", C.c_uint8 * 256),
+                ("literal", C.c_uint8 * 4), ("pad", C.c_uint8), ("unknown", C.c_uint8), ("reserved", C.c_uint8 * 2), ("aa", C.c_char * 64),
+                ("width", C.c_uint32), ("mode", C.c_uint32)]
+
+
 class SpliceRun(C.Structure):
     _fields_ = [("read", C.c_uint32), ("first", C.c_uint32), ("len", C.c_uint32), ("kind", C.c_uint32)]
 
@@ -126,6 +132,9 @@ PROTOTYPES = {
     "gmg_text_params_reference": (i32, [vp, C.c_uint32]),
     "gmg_regions_text": (i32, [vp, vp, u64, vp, vp, vp, vp, C.POINTER(C.c_size_t), vp]),
     "gmg_regions_text_device": (i32, [vp, vp, u64, vp, vp, vp, C.POINTER(vp), C.POINTER(C.c_size_t), vp]),
+    "gmg_runs_text_params_script": (i32, [vp, i32, i32]),
+    "gmg_runs_text": (i32, [vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_size_t), vp]),
+    "gmg_runs_text_device": (i32, [vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(C.c_size_t), vp]),
     "gmg_reads_splice": (i32, [vp, vp, u64, vp, u64, i32, C.POINTER(vp)]),
     "gmg_edits_plan": (i32, [vp, u64, vp, u64, vp, vp, C.c_char_p, u64, vp, u64, C.POINTER(u64), vp, vp]),
     "gmg_single_create": (i32, [C.POINTER(vp)]),

@@ -311,6 +311,56 @@ int gmg_edits_plan(const uint64_t *base_offsets, uint64_t n_reads, const gmg_edi
                    const int64_t *positions, const uint64_t *odd_base, const char *odd_letter, uint64_t n_odd,
                    gmg_splice_run *runs, uint64_t runs_cap, uint64_t *n_runs, uint64_t *string_run_off, gmg_edit_string *strings);
 
+/* ---- strings of runs as text: the .ffn and .faa files of scripts/extract_aa.py (print_frag_genes, translate) -------------------
+ * gmg_runs_text writes, over the letters of a gmg_letters, the strings a plan of runs describes (gmg_edits_plan makes one) or
+ * their translations, as gmg_regions_text writes regions: same buffers, same line rule, one kernel (k_runs_text).
+ * The printed string P_k of string k is pad_front[k] times params->pad, the bytes of runs[string_run_off[k] ..
+ * string_run_off[k + 1]) in order, and pad_behind[k] times params->pad (HOST arrays; NULL pad arrays mean 0; string_run_off
+ * ascends from 0 to n_runs: GMG_EINVAL otherwise).  Position i of a run of `len` bytes prints, with x the byte of read `read` of
+ * `letters` at the position named:
+ *   GMG_RUN_UP                 up[x],       x at first + i
+ *   GMG_RUN_DOWN               down[x],     x at first - i
+ *   GMG_RUN_SUB_UP             sub_up[x],   x at first + i
+ *   GMG_RUN_SUB_DOWN           sub_down[x], x at first - i
+ *   GMG_RUN_LITERAL + c        literal[c]; read and first are not looked at
+ *   GMG_RUN_LITERAL_AS_IS + c  up[x], x at first, `len` times: here read and first ARE looked at, unlike in gmg_reads_splice
+ * The runs obey gmg_reads_splice's rules -- nothing wraps: first + len <= read length upwards, len <= first + 1 and first < read
+ * length downwards (any first <= read length when len = 0), read < n_reads, a known kind -- and an AS_IS run with len > 0 needs
+ * read < n_reads and first < read length (with len = 0 neither is looked at): GMG_ERANGE naming the first bad run otherwise, with
+ * nothing written.  A string of 2^32 characters or more, pads included, is GMG_ERANGE as well.
+ * Record k of the text: heads[head_off[k] .. head_off[k + 1]) verbatim (as for gmg_regions_text), the record's characters with a
+ * '\n' in front of a character whenever params->width characters already stand on the line (width 0: never), and a final '\n'.
+ * The characters are, under GMG_RUNS_TEXT_DNA, the bytes of P_k; under GMG_RUNS_TEXT_PROTEIN, one per whole codon: character t
+ * translates P_k[3t .. 3t + 2], t < |P_k| / 3 rounded down (a tail of one or two bytes is dropped): aa[idx] where the three bytes
+ * are all upper-case A C G T, aa[idx] with A .. Z lowered (so '*' stays) where they are all lower-case a c g t, and `unknown` for
+ * anything else, pad bytes included; idx = 16*b0 + 4*b1 + b2 with a=0 c=1 g=2 t=3, the index of gmg_xlate_table.
+ * A mode other than the two, or a non-zero reserved byte, is GMG_EINVAL.
+ * host_out, *bytes, n_strings = 0, `stream`, the _device variant and gmg_letters_kernel_ms: exactly as for gmg_regions_text; the
+ * text buffer is the handle's one, so a text left on the device is valid until the next text call of EITHER kind on the handle.
+ * gmg_runs_text_params_script (host only) fills the script's rules: up = every byte itself, down = the script's rc() on a letter
+ * (ATCGatcg swapped, any other byte itself), sub_up = 'G' for 'C' and 'C' for anything else, sub_down = rc() of sub_up, literal =
+ * "ACGT", pad = ' ', unknown = 'X', width = 0, and aa = the script's dictionary (the standard code) for transl_table 0, else
+ * gmg_xlate_table (transl_table), whose error is passed on. */
+#define GMG_RUNS_TEXT_DNA 0
+#define GMG_RUNS_TEXT_PROTEIN 1
+typedef struct gmg_runs_text_params {
+    uint8_t up[256], down[256], sub_up[256], sub_down[256]; /* byte printed for a sequence byte, per kind of run */
+    uint8_t literal[4];   /* GMG_RUN_LITERAL + c */
+    uint8_t pad;          /* byte of a pad position */
+    uint8_t unknown;      /* protein: a codon that is neither all upper-case ACGT nor all lower-case acgt */
+    uint8_t reserved[2];  /* 0 */
+    char aa[64];          /* protein: index 16*b0 + 4*b1 + b2, a=0 c=1 g=2 t=3, as gmg_xlate_table fills it */
+    uint32_t width;       /* characters per line, 0 = one line; the line rule of gmg_regions_text */
+    uint32_t mode;
+} gmg_runs_text_params;
+int gmg_runs_text_params_script(gmg_runs_text_params *params, int mode, int transl_table);
+int gmg_runs_text(gmg_letters *letters, const gmg_splice_run *runs, uint64_t n_runs, const uint64_t *string_run_off, uint64_t n_strings,
+                  const uint32_t *pad_front, const uint32_t *pad_behind, const char *heads, const uint64_t *head_off,
+                  const gmg_runs_text_params *params, char *host_out, size_t *bytes, void *stream);
+int gmg_runs_text_device(gmg_letters *letters, const gmg_splice_run *runs, uint64_t n_runs, const uint64_t *string_run_off,
+                         uint64_t n_strings, const uint32_t *pad_front, const uint32_t *pad_behind, const char *heads,
+                         const uint64_t *head_off, const gmg_runs_text_params *params, const char **d_text, size_t *bytes, void *stream);
+
 /* ---- one string at a time ------------------------------------------------------
  * The ICM_t methods take ONE string per call (src/ICM/icm.hh:131-180).  A gmg_single keeps what such a call needs --
  * page-locked host staging, the packed read, its one segment and a result buffer on the device -- from call to call, so

@@ -7,11 +7,15 @@
 //    <prefix>.gicm        the gene ICM, build-icm -r (12 / 7 / 3), when the strings hold at least --min_icm characters
 //  <prefix> = -o, or S without its extension.
 //
-//  The edit arithmetic runs on the host (gmg_edits_plan), the strings are spliced on the device from the ingested sequences
-//  (gmg_reads_splice) and the model is trained from that batch (gmg_icm_train_reads); the text is put together from the
-//  downloaded batch, the letters that are no upper-case A C G T, and the pad counts of the plan.
+//  The edit arithmetic runs on the host (gmg_edits_plan); the text of both files is written on the device from the plan's runs
+//  and pad counts over the file's letters (gmg_runs_text: one call for the strings, one for their translations).  Only --gicm
+//  ingests the sequences and splices the strings as a batch (gmg_reads_splice, back to front) to train the model from it
+//  (gmg_icm_train_reads).
 //
-//  usage: extract-aa_gpu -s SEQS -p PREDICT [-o PREFIX] [--gicm [--min_icm N]]
+//  usage: extract-aa_gpu -s SEQS -p PREDICT [-o PREFIX] [-z N] [--gicm [--min_icm N]]
+//
+//  -z N / --transl_table N translates the .faa with GenBank table N (gmg_xlate_table) instead of the script's dictionary, the
+//  standard code: glimmer-mg predicts with table 4 on Mycoplasma classes, where TGA is read through.
 //
 //  Where the script dies this ends with status 1 and one line that names the offender: a sequence header without a record in P, a
 //  gene line without its I: D: S: fields (an empty line is one), a gene line under a header that S does not hold, a number that
@@ -35,10 +39,11 @@
 namespace {
 
 const char *kUsage =
-    "usage: extract-aa_gpu -s SEQS -p PREDICT [-o PREFIX] [--gicm [--min_icm N]]\n"
+    "usage: extract-aa_gpu -s SEQS -p PREDICT [-o PREFIX] [-z N] [--gicm [--min_icm N]]\n"
     "  -s SEQS       the sequence file the predictions were made on\n"
     "  -p PREDICT    Glimmer-MG predictions with their I: D: S: fields\n"
     "  -o PREFIX     write PREFIX.ffn and PREFIX.faa (default: SEQS without its extension)\n"
+    "  -z, --transl_table N   translate PREFIX.faa with GenBank translation table N (default: the script's table, the standard code)\n"
     "  --gicm        write PREFIX.gene.fasta instead and train PREFIX.gicm from the strings (train_features.py --indels)\n"
     "  --min_icm N   characters of gene strings needed to train the ICM (default 0)\n";
 
@@ -116,34 +121,6 @@ void ParseList(const std::string &field, const std::string &line, std::vector<in
 
 bool UpperAcgt(char ch) { return ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T'; }
 
-// the script's rc() on one letter: ATCGatcg are complemented, anything else stays
-char RcLetter(char ch)
-{
-    static const char from[] = "ATCGatcg", to[] = "TAGCtagc";
-    const char *p = ch ? strchr(from, ch) : nullptr;
-    return p ? to[p - from] : ch;
-}
-
-// translate(): the standard table on codons all in upper or all in lower case; X for anything else
-std::string Translate(const std::string &dna)
-{
-    static const char aa[] = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG", order[] = "TCAG";
-    std::string out;
-    for (size_t i = 0; i + 3 <= dna.size(); i += 3) {
-        int idx = 0, n_upper = 0, n_lower = 0;
-        for (int k = 0; k < 3 && idx >= 0; k++) {
-            const char ch = dna[i + k];
-            const char *p = ch ? strchr(order, toupper((unsigned char)ch)) : nullptr;
-            if (!p || !isalpha((unsigned char)ch)) { idx = -1; break; }
-            idx = idx * 4 + (int)(p - order);
-            if (isupper((unsigned char)ch)) n_upper++; else n_lower++;
-        }
-        if (idx < 0 || (n_upper && n_lower)) out += 'X';
-        else out += n_upper ? aa[idx] : (char)tolower((unsigned char)aa[idx]);
-    }
-    return out;
-}
-
 }  // namespace
 
 int main(int argc, char **argv)
@@ -151,6 +128,7 @@ int main(int argc, char **argv)
     std::string seq_file, predict_file, prefix;
     bool gicm = false;
     long long min_icm = 0;
+    int transl_table = 0;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], v;
         bool has_v = false;
@@ -170,6 +148,14 @@ int main(int argc, char **argv)
             char *end = nullptr;
             min_icm = strtoll(s.c_str(), &end, 10);
             if (s.empty() || *end) Die(2, "option %s: invalid integer value: '%s'", a.c_str(), s.c_str());
+        } else if (a == "-z" || a == "--transl_table") {
+            const std::string s = value();
+            char *end = nullptr;
+            const long long n = strtoll(s.c_str(), &end, 10);
+            char aa[64];
+            if (s.empty() || *end || n < 0 || n > 1000 || gmg_xlate_table((int)n, aa) != GMG_OK)
+                Die(2, "option %s: no such translation table: '%s'", a.c_str(), s.c_str());
+            transl_table = (int)n;
         } else if (a == "-h" || a == "--help") { printf("%s", kUsage); return 0; }
         else { fprintf(stderr, "%s", kUsage); Die(2, "no such option: %s", a.c_str()); }
     }
@@ -276,13 +262,33 @@ int main(int argc, char **argv)
         runs.resize(n_runs);
     }
 
-    // ---- the strings, on the device
+    // ---- what is printed: the record names, the pads, and -- for --min_icm -- the script's count of every string, len(line.rstrip()):
+    //      the pad in front counts where a run follows it, the pad behind never does (no run prints white space)
+    std::string heads;
+    std::vector<uint64_t> head_off(n_genes + 1, 0);
+    std::vector<uint32_t> pad_front(n_genes ? n_genes : 1), pad_behind(n_genes ? n_genes : 1);
+    unsigned long long printed = 0;
+    for (uint64_t k = 0; k < n_genes; k++) {
+        const gmg_edit_string &e = strings[k];
+        char name[64];
+        snprintf(name, sizeof name, "_%lld,%lld_%c\n", (long long)e.start, (long long)e.end, e.strand > 0 ? '+' : '-');
+        heads += ">" + headers[genes[e.gene].read] + name;
+        head_off[k + 1] = heads.size();
+        pad_front[k] = e.pad_front;
+        pad_behind[k] = e.pad_behind;
+        unsigned long long in_runs = 0;
+        for (uint64_t q = sro[k]; q < sro[k + 1]; q++) in_runs += runs[q].len;
+        if (in_runs) printed += e.pad_front + in_runs;
+    }
+
+    // ---- the device: the letters for the text; the ingested codes only where the gene ICM is trained from them
     const char *dev = getenv("GMG_DEVICE");
     Check(gmg_init(dev ? atoi(dev) : 0), "gmg_init");
-    gmg_reads *reads = nullptr, *spliced = nullptr;
-    gmg_fasta *index = nullptr;
-    Check(gmg_fasta_ingest(seq_bytes.data(), seq_bytes.size(), &reads, &index), "gmg_fasta_ingest");
-    {
+    const bool train = gicm && (long long)printed >= min_icm;
+    gmg_reads *reads = nullptr;
+    if (train) {
+        gmg_fasta *index = nullptr;
+        Check(gmg_fasta_ingest(seq_bytes.data(), seq_bytes.size(), &reads, &index), "gmg_fasta_ingest");
         uint64_t n = 0, total = 0;
         Check(gmg_fasta_info(index, &n, &total, nullptr), "gmg_fasta_info");
         if (n != n_reads || total != letters.size()) Die(1, "%s: the records of the file are not one header line and lines of letters each", seq_file.c_str());
@@ -290,43 +296,27 @@ int main(int argc, char **argv)
         std::vector<uint64_t> dev_off(n + 1);
         Check(gmg_reads_download(reads, packed.data(), dev_off.data()), "gmg_reads_download");
         if (dev_off != off) Die(1, "%s: the records of the file are not one header line and lines of letters each", seq_file.c_str());
+        gmg_fasta_free(index);
     }
-    gmg_fasta_free(index);
-    Check(gmg_reads_splice(reads, runs.data(), n_runs, sro.data(), n_genes, 0, &spliced), "gmg_reads_splice");
-    uint64_t n_strings = 0, total = 0;
-    Check(gmg_reads_info(spliced, &n_strings, &total), "gmg_reads_info");
-    std::vector<uint32_t> packed(gmg_packed_words(total));
-    std::vector<uint64_t> new_off(n_strings + 1);
-    Check(gmg_reads_download(spliced, packed.data(), new_off.data()), "gmg_reads_download");
-    gmg_reads_free(spliced);
 
-    // ---- the text: the code of every base from the batch; the letter itself where it is no upper-case A C G T and was copied
-    std::string ffn, faa, dna;
-    unsigned long long printed = 0;
-    for (uint64_t k = 0; k < n_genes; k++) {
-        const gmg_edit_string &e = strings[k];
-        dna.assign(e.pad_front, ' ');
-        uint64_t at = new_off[k];
-        for (uint64_t q = sro[k]; q < sro[k + 1]; q++) {
-            const gmg_splice_run &r = runs[q];
-            for (uint32_t i = 0; i < r.len; i++, at++) {
-                char ch = "ACGT"[(packed[at >> 4] >> (2 * (at & 15))) & 3];
-                if (r.kind == GMG_RUN_UP || r.kind == GMG_RUN_DOWN || r.kind >= GMG_RUN_LITERAL_AS_IS) {
-                    const uint64_t b = off[r.read] + (r.kind == GMG_RUN_UP ? r.first + i : r.kind == GMG_RUN_DOWN ? r.first - i : r.first);
-                    if (!UpperAcgt(letters[b])) ch = r.kind == GMG_RUN_DOWN ? RcLetter(letters[b]) : letters[b];
-                }
-                dna += ch;
-            }
+    // ---- the text, written on the device: the strings themselves, and their translations
+    gmg_letters *on_device = nullptr;
+    Check(gmg_letters_upload(letters.data(), off.data(), n_reads, &on_device), "gmg_letters_upload");
+    auto text = [&](int mode) {
+        gmg_runs_text_params prm;
+        Check(gmg_runs_text_params_script(&prm, mode, transl_table), "gmg_runs_text_params_script");
+        std::string out;
+        size_t bytes = 0;
+        for (int pass = 0; pass < 2; pass++) {          // the length, then the text
+            Check(gmg_runs_text(on_device, runs.data(), n_runs, sro.data(), n_genes, pad_front.data(), pad_behind.data(), heads.data(),
+                                head_off.data(), &prm, pass ? &out[0] : nullptr, &bytes, nullptr), "gmg_runs_text");
+            if (bytes == 0) break;
+            out.resize(bytes);
         }
-        if (at != new_off[k + 1]) Die(1, "the spliced batch and the plan disagree about the length of a string");
-        dna.append(e.pad_behind, ' ');
-        char name[64];
-        snprintf(name, sizeof name, "_%lld,%lld_%c\n", (long long)e.start, (long long)e.end, e.strand > 0 ? '+' : '-');
-        const std::string head = ">" + headers[genes[e.gene].read] + name;
-        ffn += head + dna + "\n";
-        if (!gicm) faa += head + Translate(dna) + "\n";
-        printed += RStrip(dna, 0, dna.size());
-    }
+        return out;
+    };
+    const std::string ffn = text(GMG_RUNS_TEXT_DNA), faa = gicm ? std::string() : text(GMG_RUNS_TEXT_PROTEIN);
+    gmg_letters_free(on_device);
 
     if (!gicm) {
         WriteFile(prefix + ".faa", faa);
@@ -336,7 +326,7 @@ int main(int argc, char **argv)
         unlink((prefix + ".faa").c_str());
         unlink((prefix + ".ffn").c_str());
         WriteFile(prefix + ".gene.fasta", ffn);
-        if ((long long)printed >= min_icm) {
+        if (train) {
             gmg_reads *reversed = nullptr;
             Check(gmg_reads_splice(reads, runs.data(), n_runs, sro.data(), n_genes, GMG_EXTRACT_REVERSED, &reversed), "gmg_reads_splice");
             gmg_icm *icm = nullptr;
