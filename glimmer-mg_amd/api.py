@@ -605,16 +605,25 @@ class Letters:
     """gmg_letters: the sequence bytes of a batch in HBM, one per base, and the text of regions of them (gmg_regions_text)"""
 
     def __init__(self, letters, offsets):
-        letters = bytes(letters)
+        """letters: bytes, or a uint8 array (uploaded from where it lies: no copy of a batch of gigabytes)"""
         self.offsets = np.ascontiguousarray(offsets, np.uint64)
-        assert len(letters) == int(self.offsets[-1])
         self.h = C.c_void_p()
+        if isinstance(letters, np.ndarray):
+            letters = np.ascontiguousarray(letters, np.uint8)
+            assert letters.size == int(self.offsets[-1])
+            _ck(capi.lib().gmg_letters_upload(_ptr(letters), _ptr(self.offsets), len(self.offsets) - 1, C.byref(self.h)))
+            return
+        letters = bytes(letters)
+        assert len(letters) == int(self.offsets[-1])
         _ck(capi.lib().gmg_letters_upload(letters, _ptr(self.offsets), len(self.offsets) - 1, C.byref(self.h)))
 
     @staticmethod
     def _args(regions, heads):
         """regions [(read, first, len, strand)] or a GeneRegion array; heads: a list of bytes, or (blob, offsets)"""
         n = len(regions)
+        if isinstance(regions, np.ndarray):              # int [n, 4]: the bytes of a gmg_gene_region array
+            regions = np.ascontiguousarray(regions.reshape(-1, 4), np.int32)
+            regions = (capi.GeneRegion * max(n, 1)).from_buffer_copy(regions.tobytes() if n else bytes(C.sizeof(capi.GeneRegion)))
         if not isinstance(regions, C.Array):
             regions = (capi.GeneRegion * max(n, 1))(*[capi.GeneRegion(*[int(x) for x in r]) for r in regions])
         if isinstance(heads, tuple):
