@@ -91,17 +91,17 @@ class _DeviceBuffer:
         _ck(capi.lib().gmg_device_malloc(C.byref(self.ptr), self.nbytes))
 
     @classmethod
-    def from_host(cls, arr):
+    def from_host(cls, arr, stream=None):
         arr = np.ascontiguousarray(arr)
         buf = cls(max(arr.nbytes, 1))
         if arr.nbytes:
-            _ck(capi.lib().gmg_memcpy_h2d(buf.ptr, _ptr(arr), arr.nbytes, None))
+            _ck(capi.lib().gmg_memcpy_h2d(buf.ptr, _ptr(arr), arr.nbytes, stream))
         return buf
 
-    def to_host(self, dtype, count):
+    def to_host(self, dtype, count, stream=None):
         out = np.empty(count, dtype)
         if out.nbytes:
-            _ck(capi.lib().gmg_memcpy_d2h(_ptr(out), self.ptr, out.nbytes, None))
+            _ck(capi.lib().gmg_memcpy_d2h(_ptr(out), self.ptr, out.nbytes, stream))
         return out
 
     def free(self):
@@ -357,14 +357,14 @@ class Reads:
         return cls(*pack_strings(seqs))
 
     @classmethod
-    def from_fasta_bytes(cls, data):
-        """gmg_fasta_ingest: the file's bytes are parsed on the device (Fasta_Read + Filter + tolower + 2-bit packing).
-        -> (Reads, headers [bytes], gc_count)"""
+    def from_fasta_bytes(cls, data, stream=None):
+        """gmg_fasta_ingest_on: the file's bytes are parsed on the device (Fasta_Read + Filter + tolower + 2-bit packing), every copy
+        and kernel on `stream`.  -> (Reads, headers [bytes], gc_count)"""
         data = bytes(data)
         self = cls.__new__(cls)
         self.h = C.c_void_p()
         index = C.c_void_p()
-        _ck(capi.lib().gmg_fasta_ingest(data, len(data), C.byref(self.h), C.byref(index)))
+        _ck(capi.lib().gmg_fasta_ingest_on(data, len(data), C.byref(self.h), C.byref(index), stream))
         try:
             n, total, gc = C.c_uint64(), C.c_uint64(), C.c_uint64()
             _ck(capi.lib().gmg_fasta_info(index, C.byref(n), C.byref(total), C.byref(gc)))
@@ -644,7 +644,7 @@ class Letters:
         """gmg_regions_text with host_out = NULL: the length of the text"""
         return self._size(*self._args(regions, heads), params)
 
-    def regions_text(self, regions, heads, params, capacity=None, out=None):
+    def regions_text(self, regions, heads, params, capacity=None, out=None, stream=None):
         """gmg_regions_text -> the text (bytes).  capacity: the size of the host buffer (default: what text_size says); out: a
         uint8 array to write into instead (its size is the capacity), then the length is returned"""
         regions, n, blob, off = self._args(regions, heads)
@@ -655,14 +655,14 @@ class Letters:
         else:
             buf, capacity = out, out.size
         size = C.c_size_t(int(capacity))
-        _ck(capi.lib().gmg_regions_text(self.h, regions, n, blob, _ptr(off), C.byref(params), _ptr(buf), C.byref(size), None))
+        _ck(capi.lib().gmg_regions_text(self.h, regions, n, blob, _ptr(off), C.byref(params), _ptr(buf), C.byref(size), stream))
         return size.value if out is not None else buf[:size.value].tobytes()
 
-    def regions_text_device(self, regions, heads, params):
+    def regions_text_device(self, regions, heads, params, stream=None):
         """gmg_regions_text_device -> (device pointer, bytes): the text stays in the handle's buffer until the next call"""
         regions, n, blob, off = self._args(regions, heads)
         ptr, size = C.c_void_p(), C.c_size_t(0)
-        _ck(capi.lib().gmg_regions_text_device(self.h, regions, n, blob, _ptr(off), C.byref(params), C.byref(ptr), C.byref(size), None))
+        _ck(capi.lib().gmg_regions_text_device(self.h, regions, n, blob, _ptr(off), C.byref(params), C.byref(ptr), C.byref(size), stream))
         return ptr, size.value
 
     @staticmethod
@@ -691,7 +691,7 @@ class Letters:
         _ck(capi.lib().gmg_runs_text(self.h, *args, C.byref(params), None, C.byref(size), None))
         return size.value
 
-    def runs_text(self, runs, string_run_off, heads, params, pad_front=None, pad_behind=None, capacity=None, out=None):
+    def runs_text(self, runs, string_run_off, heads, params, pad_front=None, pad_behind=None, capacity=None, out=None, stream=None):
         """gmg_runs_text -> the text (bytes): string k = pad_front[k] pad bytes, runs[string_run_off[k] : string_run_off[k + 1]],
         pad_behind[k] pad bytes, or its translation (runs_text_params).  capacity / out as for regions_text"""
         keep, args = self._run_args(runs, string_run_off, heads, pad_front, pad_behind)
@@ -704,14 +704,14 @@ class Letters:
         else:
             buf, capacity = out, out.size
         size = C.c_size_t(int(capacity))
-        _ck(capi.lib().gmg_runs_text(self.h, *args, C.byref(params), _ptr(buf), C.byref(size), None))
+        _ck(capi.lib().gmg_runs_text(self.h, *args, C.byref(params), _ptr(buf), C.byref(size), stream))
         return size.value if out is not None else buf[:size.value].tobytes()
 
-    def runs_text_device(self, runs, string_run_off, heads, params, pad_front=None, pad_behind=None):
+    def runs_text_device(self, runs, string_run_off, heads, params, pad_front=None, pad_behind=None, stream=None):
         """gmg_runs_text_device -> (device pointer, bytes): the text stays in the handle's buffer until the next text call"""
         keep, args = self._run_args(runs, string_run_off, heads, pad_front, pad_behind)
         ptr, size = C.c_void_p(), C.c_size_t(0)
-        _ck(capi.lib().gmg_runs_text_device(self.h, *args, C.byref(params), C.byref(ptr), C.byref(size), None))
+        _ck(capi.lib().gmg_runs_text_device(self.h, *args, C.byref(params), C.byref(ptr), C.byref(size), stream))
         return ptr, size.value
 
     def kernel_ms(self):
@@ -731,11 +731,11 @@ class Letters:
             pass
 
 
-def memcpy_d2h(ptr, nbytes):
-    """nbytes of device memory at ptr as bytes (gmg_memcpy_d2h)"""
+def memcpy_d2h(ptr, nbytes, stream=None):
+    """nbytes of device memory at ptr as bytes (gmg_memcpy_d2h on `stream`, waited for)"""
     out = np.empty(max(int(nbytes), 1), np.uint8)
     if nbytes:
-        _ck(capi.lib().gmg_memcpy_d2h(_ptr(out), ptr, int(nbytes), None))
+        _ck(capi.lib().gmg_memcpy_d2h(_ptr(out), ptr, int(nbytes), stream))
     return out[:int(nbytes)].tobytes()
 
 
@@ -825,50 +825,55 @@ def frame_score6(gene, null, reads, d_out=None, stream=None, row_stride=None, re
     buf = _DeviceBuffer(6 * max(stride, 1) * 8)
     call(buf.ptr)
     _ck(capi.lib().gmg_synchronize(stream))
-    out = buf.to_host(np.float64, 6 * stride).reshape(6, stride)[:, :reads.total_bases].copy()
+    out = buf.to_host(np.float64, 6 * stride, stream).reshape(6, stride)[:, :reads.total_bases].copy()
     buf.free()
     return out
 
 
-def _seg_call(fn, model, reads, segs, frame, count):
+def _seg_call(fn, model, reads, segs, frame, count, d_out=None, stream=None):
+    """every per-segment call: on `stream`; with d_out (a device pointer to `count` doubles) asynchronous, returns None"""
+    if d_out is not None:
+        _ck(fn(model.device(), reads.h, segs.h, int(frame), C.c_void_p(d_out), stream))
+        return None
     buf = _DeviceBuffer(max(count, 1) * 8)
-    _ck(fn(model.device(), reads.h, segs.h, int(frame), buf.ptr, None))
-    _ck(capi.lib().gmg_synchronize(None))
-    out = buf.to_host(np.float64, count)
+    _ck(fn(model.device(), reads.h, segs.h, int(frame), buf.ptr, stream))
+    out = buf.to_host(np.float64, count, stream)
     buf.free()
     return out
 
 
-def segment_frame_score(model, reads, segs, frame):
+def segment_frame_score(model, reads, segs, frame, d_out=None, stream=None):
     """ICM_t::Frame_Score (icm.cc:485-509) per segment, flat float64[total_len]"""
-    return _seg_call(capi.lib().gmg_segment_frame_score, model, reads, segs, frame, segs.total_len)
+    return _seg_call(capi.lib().gmg_segment_frame_score, model, reads, segs, frame, segs.total_len, d_out, stream)
 
 
-def segment_cumscore(model, reads, segs, frame0):
+def segment_cumscore(model, reads, segs, frame0, d_out=None, stream=None):
     """ICM_t::Cumulative_Score (icm.cc:354-405) per segment, flat float64[total_len]"""
-    return _seg_call(capi.lib().gmg_segment_cumscore, model, reads, segs, frame0, segs.total_len)
+    return _seg_call(capi.lib().gmg_segment_cumscore, model, reads, segs, frame0, segs.total_len, d_out, stream)
 
 
-def score_string(model, reads, segs, frame0):
+def score_string(model, reads, segs, frame0, d_out=None, stream=None):
     """ICM_t::Score_String (icm.cc:864-903) per segment, float64[n]"""
-    return _seg_call(capi.lib().gmg_score_string, model, reads, segs, frame0, segs.n)
+    return _seg_call(capi.lib().gmg_score_string, model, reads, segs, frame0, segs.n, d_out, stream)
 
 
-def segment_partial_prob(model, reads, segs, frame):
+def segment_partial_prob(model, reads, segs, frame, d_out=None, stream=None):
     """ICM_t::Partial_Window_Prob (icm.cc:807-842) of each segment's last base, float64[n]"""
-    return _seg_call(capi.lib().gmg_segment_partial_prob, model, reads, segs, frame, segs.n)
+    return _seg_call(capi.lib().gmg_segment_partial_prob, model, reads, segs, frame, segs.n, d_out, stream)
 
 
-def all_frame_score(gene, reads, segs, prefix_len, frames):
-    """All_Frame_Score (glimmer3.cc:328-359) per segment -> float64[n, 6]"""
-    pre = _DeviceBuffer.from_host(np.asarray(prefix_len, np.uint32))
-    frs = _DeviceBuffer.from_host(np.asarray(frames, np.int32))
-    buf = _DeviceBuffer(max(segs.n, 1) * 48)
-    _ck(capi.lib().gmg_all_frame_score(gene.device(), reads.h, segs.h, pre.ptr, frs.ptr, buf.ptr, None))
-    _ck(capi.lib().gmg_synchronize(None))
-    out = buf.to_host(np.float64, 6 * segs.n).reshape(segs.n, 6)
+def all_frame_score(gene, reads, segs, prefix_len, frames, d_out=None, stream=None):
+    """All_Frame_Score (glimmer3.cc:328-359) per segment -> float64[n, 6]; with d_out (a device pointer to 6 n doubles) the result
+    stays there and None is returned (the two input arrays are uploaded and released behind the stream's work)"""
+    pre = _DeviceBuffer.from_host(np.asarray(prefix_len, np.uint32), stream)
+    frs = _DeviceBuffer.from_host(np.asarray(frames, np.int32), stream)
+    buf = _DeviceBuffer(max(segs.n, 1) * 48) if d_out is None else None
+    _ck(capi.lib().gmg_all_frame_score(gene.device(), reads.h, segs.h, pre.ptr, frs.ptr, buf.ptr if buf else C.c_void_p(d_out), stream))
+    _ck(capi.lib().gmg_synchronize(stream))
+    out = buf.to_host(np.float64, 6 * segs.n, stream).reshape(segs.n, 6) if buf else None
     for b in (pre, frs, buf):
-        b.free()
+        if b:
+            b.free()
     return out
 
 
@@ -881,7 +886,7 @@ ORF_RESULT_DTYPE = np.dtype([("gene_score", "<f8"), ("best_score", "<f8"), ("sta
 
 
 def score_orfs(gene, null, reads, orfs, min_gene_len=75, allow_truncated=False, use_first_start=False,
-               ignore_score_len=2**31 - 1, start_threshold=-6.0, start_codons=("atg", "gtg", "ttg")):
+               ignore_score_len=2**31 - 1, start_threshold=-6.0, start_codons=("atg", "gtg", "ttg"), stream=None):
     """The scoring part of Score_Orfs (glimmer3.cc:1275-1552) for a batch of ORFs.
     orfs: rows (read, frame, stop_position, orf_len) as Find_Orfs produced them.
     -> (results[ORF_RESULT_DTYPE], starts[START_DTYPE]); ORF i's starts are
@@ -900,9 +905,9 @@ def score_orfs(gene, null, reads, orfs, min_gene_len=75, allow_truncated=False, 
     res = np.zeros(len(o), ORF_RESULT_DTYPE)
     try:
         n_st = C.c_uint64()
-        _ck(capi.lib().gmg_score_orfs_begin(gene.device(), null.device(), reads.h, batch, C.byref(prm), C.byref(n_st), None))
+        _ck(capi.lib().gmg_score_orfs_begin(gene.device(), null.device(), reads.h, batch, C.byref(prm), C.byref(n_st), stream))
         starts = np.zeros(max(int(n_st.value), 1), START_DTYPE)
-        _ck(capi.lib().gmg_score_orfs_fetch(batch, _ptr(res), _ptr(starts), None))
+        _ck(capi.lib().gmg_score_orfs_fetch(batch, _ptr(res), _ptr(starts), stream))
     finally:
         capi.lib().gmg_orf_batch_free(batch)
     return res, starts
@@ -915,7 +920,7 @@ MG_ORF_DTYPE = np.dtype([("read", "<u4"), ("frame", "<i4"), ("stop_position", "<
 
 
 def find_orfs(reads, min_gene_len=75, allow_truncated=False, start_codons=("atg", "gtg", "ttg"),
-              stop_codons=("taa", "tag", "tga"), circular=False, ignore_regions=()):
+              stop_codons=("taa", "tag", "tga"), circular=False, ignore_regions=(), stream=None):
     """gmg_find_orfs: Find_Orfs for every read -> (orfs[MG_ORF_DTYPE], read_orf_off[uint64 n_reads+1]).
     circular: Genome_Is_Circular; ignore_regions: [(lo, hi)] as Get_Ignore_Regions leaves them (0-based lo, hi one past the end)"""
     prm = capi.MgParams(min_gene_len, int(allow_truncated), 2**31 - 1, len(start_codons), len(stop_codons), 0, 0.0)
@@ -930,13 +935,13 @@ def find_orfs(reads, min_gene_len=75, allow_truncated=False, start_codons=("atg"
     if len(lo):
         prm.ignore_lo, prm.ignore_hi = lo.ctypes.data, hi.ctypes.data
     res = C.c_void_p()
-    _ck(capi.lib().gmg_find_orfs(reads.h, C.byref(prm), C.byref(res), None))
+    _ck(capi.lib().gmg_find_orfs(reads.h, C.byref(prm), C.byref(res), stream))
     try:
         n_orfs, n_starts = C.c_uint64(), C.c_uint64()
         _ck(capi.lib().gmg_mg_result_info(res, C.byref(n_orfs), C.byref(n_starts)))
         orfs = np.zeros(max(n_orfs.value, 1), MG_ORF_DTYPE)
         off = np.zeros(reads.n_reads + 1, np.uint64)
-        _ck(capi.lib().gmg_mg_result_fetch(res, _ptr(orfs), None, _ptr(off)))
+        _ck(capi.lib().gmg_mg_result_fetch_on(res, _ptr(orfs), None, _ptr(off), stream))
     finally:
         capi.lib().gmg_mg_result_free(res)
     return orfs[:n_orfs.value], off
@@ -946,7 +951,7 @@ class OrfResult:
     """A gmg_find_orfs result that stays on the device (gmg_mg_result): what gmg_entropy_orfs reads.  fetch() -> (orfs, read_orf_off)"""
 
     def __init__(self, reads, min_gene_len=75, allow_truncated=False, start_codons=("atg", "gtg", "ttg"),
-                 stop_codons=("taa", "tag", "tga"), circular=False):
+                 stop_codons=("taa", "tag", "tga"), circular=False, stream=None):
         prm = capi.MgParams(min_gene_len, int(allow_truncated), 2**31 - 1, len(start_codons), len(stop_codons), 0, 0.0)
         for i, c in enumerate(start_codons):
             prm.start_codon[i].value = c.encode()
@@ -955,7 +960,8 @@ class OrfResult:
         prm.circular = int(bool(circular))
         self.h = C.c_void_p()
         self.n_reads = reads.n_reads
-        _ck(capi.lib().gmg_find_orfs(reads.h, C.byref(prm), C.byref(self.h), None))
+        self.stream = stream
+        _ck(capi.lib().gmg_find_orfs(reads.h, C.byref(prm), C.byref(self.h), stream))
         n_orfs, n_starts = C.c_uint64(), C.c_uint64()
         _ck(capi.lib().gmg_mg_result_info(self.h, C.byref(n_orfs), C.byref(n_starts)))
         self.n_orfs = int(n_orfs.value)
@@ -963,7 +969,7 @@ class OrfResult:
     def fetch(self):
         orfs = np.zeros(max(self.n_orfs, 1), MG_ORF_DTYPE)
         off = np.zeros(self.n_reads + 1, np.uint64)
-        _ck(capi.lib().gmg_mg_result_fetch(self.h, _ptr(orfs), None, _ptr(off)))
+        _ck(capi.lib().gmg_mg_result_fetch_on(self.h, _ptr(orfs), None, _ptr(off), self.stream))
         return orfs[:self.n_orfs], off
 
     def close(self):
@@ -1005,15 +1011,14 @@ def entropy_from_counts(counts, pos, neg):
     return out.reshape(counts.shape[:-1] + (3,))
 
 
-def _entropy_call(n, want_counts, want_dist, call):
+def _entropy_call(n, want_counts, want_dist, call, stream=None):
     """runs call(d_counts, d_dist) with device buffers for n rows -> (counts int32 [n, 20] or None, dist float64 [n, 3] or None)"""
     cbuf = _DeviceBuffer(max(n, 1) * 80) if want_counts else None
     dbuf = _DeviceBuffer(max(n, 1) * 24) if want_dist else None
     try:
         _ck(call(cbuf.ptr if cbuf else None, dbuf.ptr if dbuf else None))
-        _ck(capi.lib().gmg_synchronize(None))
-        counts = cbuf.to_host(np.int32, n * 20).reshape(n, 20) if cbuf else None
-        dist = dbuf.to_host(np.float64, n * 3).reshape(n, 3) if dbuf else None
+        counts = cbuf.to_host(np.int32, n * 20, stream).reshape(n, 20) if cbuf else None
+        dist = dbuf.to_host(np.float64, n * 3, stream).reshape(n, 3) if dbuf else None
     finally:
         for b in (cbuf, dbuf):
             if b:
@@ -1021,21 +1026,29 @@ def _entropy_call(n, want_counts, want_dist, call):
     return counts, dist
 
 
-def entropy_regions(reads, regions, aa, pos, neg, want_counts=True, want_dist=True):
-    """gmg_entropy_regions: regions = [(read, first, len, strand)] -> (counts [n, 20] or None, dist [n, 3] or None)"""
+def entropy_regions(reads, regions, aa, pos, neg, want_counts=True, want_dist=True, stream=None, d_counts=None, d_dist=None):
+    """gmg_entropy_regions: regions = [(read, first, len, strand)] -> (counts [n, 20] or None, dist [n, 3] or None); with d_counts or
+    d_dist (device pointers) the call is asynchronous on `stream`, the rows stay there and None is returned"""
     arr = (capi.GeneRegion * max(len(regions), 1))(*[capi.GeneRegion(int(r), int(f), int(ln), int(s)) for r, f, ln, s in regions])
     aa = bytes(aa)
     pos, neg = np.ascontiguousarray(pos, np.float64), np.ascontiguousarray(neg, np.float64)
+    if d_counts is not None or d_dist is not None:
+        _ck(capi.lib().gmg_entropy_regions(reads.h, arr, len(regions), aa, _ptr(pos), _ptr(neg), d_counts, d_dist, stream))
+        return None
     return _entropy_call(len(regions), want_counts, want_dist, lambda c, d: capi.lib().gmg_entropy_regions(
-        reads.h, arr, len(regions), aa, _ptr(pos), _ptr(neg), c, d, None))
+        reads.h, arr, len(regions), aa, _ptr(pos), _ptr(neg), c, d, stream), stream)
 
 
-def entropy_orfs(reads, orf_result, aa, pos, neg, want_counts=True, want_dist=True):
-    """gmg_entropy_orfs on an OrfResult -> (counts [n_orfs, 20] or None, dist [n_orfs, 3] or None)"""
+def entropy_orfs(reads, orf_result, aa, pos, neg, want_counts=True, want_dist=True, stream=None, d_counts=None, d_dist=None):
+    """gmg_entropy_orfs on an OrfResult -> (counts [n_orfs, 20] or None, dist [n_orfs, 3] or None); d_counts / d_dist as for
+    entropy_regions"""
     aa = bytes(aa)
     pos, neg = np.ascontiguousarray(pos, np.float64), np.ascontiguousarray(neg, np.float64)
+    if d_counts is not None or d_dist is not None:
+        _ck(capi.lib().gmg_entropy_orfs(reads.h, orf_result.h, aa, _ptr(pos), _ptr(neg), d_counts, d_dist, stream))
+        return None
     return _entropy_call(orf_result.n_orfs, want_counts, want_dist, lambda c, d: capi.lib().gmg_entropy_orfs(
-        reads.h, orf_result.h, aa, _ptr(pos), _ptr(neg), c, d, None))
+        reads.h, orf_result.h, aa, _ptr(pos), _ptr(neg), c, d, stream), stream)
 
 
 AUDIT_NEXT_STOP = 1                                     # GMG_AUDIT_NEXT_STOP
@@ -1215,7 +1228,7 @@ def mg_score_reads(gene, null, reads, min_gene_len=75, allow_truncated=True, ign
                    start_threshold=-6.0, start_codons=("atg", "gtg", "ttg"), stop_codons=("taa", "tag", "tga"),
                    frame_scores=None, accepted_only=False, allow_indels=False, allow_subs=False, quality=None,
                    min_indel_orf_len=15, indel_quality_threshold=18, indel_max=2, indel_suffix_score_threshold=-12.0,
-                   read_null=None, read_ignore_score_len=None, groups=None):
+                   read_null=None, read_ignore_score_len=None, groups=None, stream=None):
     """glimmer-mg's front half for a batch of reads (include/gmg.h: gmg_mg_score_reads): Score_All_Frames,
     Find_Orfs, Score_Orf_Starts and the filter of Score_Orfs_Errors.
     -> (orfs[MG_ORF_DTYPE], starts[START_DTYPE], read_orf_off[uint64 n_reads+1]).
@@ -1252,17 +1265,17 @@ def mg_score_reads(gene, null, reads, min_gene_len=75, allow_truncated=True, ign
     res = C.c_void_p()
     if groups is not None:                              # gmg_mg_score_groups: [(Icm, read_begin, read_end), ...], `gene` is not used
         arr = (capi.MgGroup * max(len(groups), 1))(*[capi.MgGroup(m.device(), int(b), int(e)) for m, b, e in groups])
-        _ck(capi.lib().gmg_mg_score_groups(arr, len(groups), null_model.device(), reads.h, C.byref(prm), C.byref(res), None))
+        _ck(capi.lib().gmg_mg_score_groups(arr, len(groups), null_model.device(), reads.h, C.byref(prm), C.byref(res), stream))
     else:
         _ck(capi.lib().gmg_mg_score_reads(gene.device(), null_model.device(), reads.h, C.byref(prm),
-                                          frame_scores.ptr if frame_scores is not None else None, C.byref(res), None))
+                                          frame_scores.ptr if frame_scores is not None else None, C.byref(res), stream))
     try:
         n_orfs, n_starts = C.c_uint64(), C.c_uint64()
         _ck(capi.lib().gmg_mg_result_info(res, C.byref(n_orfs), C.byref(n_starts)))
         orfs = np.zeros(max(n_orfs.value, 1), MG_ORF_DTYPE)
         starts = np.zeros(max(n_starts.value, 1), START_DTYPE)
         off = np.zeros(reads.n_reads + 1, np.uint64)
-        _ck(capi.lib().gmg_mg_result_fetch(res, _ptr(orfs), _ptr(starts), _ptr(off)))
+        _ck(capi.lib().gmg_mg_result_fetch_on(res, _ptr(orfs), _ptr(starts), _ptr(off), stream))
         if err:
             errs = np.zeros(max(n_starts.value, 1), START_ERRORS_DTYPE)
             _ck(capi.lib().gmg_mg_result_fetch_errors(res, _ptr(errs)))
@@ -1273,14 +1286,17 @@ def mg_score_reads(gene, null, reads, min_gene_len=75, allow_truncated=True, ign
     return orfs[:n_orfs.value], starts[:n_starts.value], off
 
 
-def score_reads_strings(models, reads):
-    """gmg_score_reads_strings: whole-read Score_String (frame 0) of every read and of its reverse complement under
-    every model -> float64 [n_models, n_reads, 2]"""
+def score_reads_strings(models, reads, d_out=None, stream=None):
+    """gmg_score_reads_strings on `stream`: whole-read Score_String (frame 0) of every read and of its reverse complement under
+    every model -> float64 [n_models, n_reads, 2]; with d_out (a device pointer to that many doubles) the sums stay there"""
     n = len(models)
     arr = (C.c_void_p * max(n, 1))(*[m.device() for m in models])
+    if d_out is not None:
+        _ck(capi.lib().gmg_score_reads_strings(arr, n, reads.h, C.c_void_p(d_out), stream))
+        return None
     buf = _DeviceBuffer(max(n * reads.n_reads * 2, 1) * 8)
-    _ck(capi.lib().gmg_score_reads_strings(arr, n, reads.h, buf.ptr, None))
-    out = buf.to_host(np.float64, n * reads.n_reads * 2).reshape(n, reads.n_reads, 2)
+    _ck(capi.lib().gmg_score_reads_strings(arr, n, reads.h, buf.ptr, stream))
+    out = buf.to_host(np.float64, n * reads.n_reads * 2, stream).reshape(n, reads.n_reads, 2)
     buf.free()
     return out
 
@@ -1304,30 +1320,29 @@ class TopHits:
         assert len(inf) == B
         return inf, _ptr(inf)
 
-    def update_sums(self, sums, first_model=0, informative=None, forward_only=False):
-        """gmg_tophits_update_sums on HOST sums float64 [B, n_reads, 2] (uploaded first)"""
+    def update_sums(self, sums, first_model=0, informative=None, forward_only=False, stream=None):
+        """gmg_tophits_update_sums on HOST sums float64 [B, n_reads, 2] (uploaded first, on the same stream)"""
         sums = np.ascontiguousarray(sums, np.float64)
         B = sums.shape[0]
-        buf = _DeviceBuffer.from_host(sums)
+        buf = _DeviceBuffer.from_host(sums, stream)
         inf, p = self._inf(informative, B)
         try:
-            _ck(capi.lib().gmg_tophits_update_sums(self.h, buf.ptr, B, int(first_model), p, int(bool(forward_only)), None))
+            _ck(capi.lib().gmg_tophits_update_sums(self.h, buf.ptr, B, int(first_model), p, int(bool(forward_only)), stream))
         finally:
             buf.free()
 
-    def scores(self, models, first_model=0, informative=None, forward_only=False, return_sums=False):
+    def scores(self, models, first_model=0, informative=None, forward_only=False, return_sums=False, stream=None):
         """gmg_tophits_scores: the models scored on the device into the handle's scratch, then the update; return_sums: the
         scratch copied back, float64 [B, n_reads, 2]"""
         B = len(models)
         arr = (C.c_void_p * max(B, 1))(*[m.device() for m in models])
         inf, p = self._inf(informative, B)
         d = C.c_void_p()
-        _ck(capi.lib().gmg_tophits_scores(self.h, arr, B, int(first_model), p, int(bool(forward_only)), None, C.byref(d)))
+        _ck(capi.lib().gmg_tophits_scores(self.h, arr, B, int(first_model), p, int(bool(forward_only)), stream, C.byref(d)))
         if return_sums:
             out = np.empty(B * self.reads.n_reads * 2, np.float64)
             if out.nbytes:
-                _ck(capi.lib().gmg_memcpy_d2h(_ptr(out), d, out.nbytes, None))
-                _ck(capi.lib().gmg_synchronize(None))
+                _ck(capi.lib().gmg_memcpy_d2h(_ptr(out), d, out.nbytes, stream))
             return out.reshape(B, self.reads.n_reads, 2)
 
     def fetch(self):
@@ -1338,16 +1353,16 @@ class TopHits:
         _ck(capi.lib().gmg_tophits_fetch(self.h, _ptr(keys), _ptr(models)))
         return keys[:n], models[:n]
 
-    def format_rows(self, sums, forward_only=False):
+    def format_rows(self, sums, forward_only=False, stream=None):
         """gmg_tophits_format_rows on HOST sums float64 [B, n_reads, 2] -> the B data-matrix lines (bytes)"""
         sums = np.ascontiguousarray(sums, np.float64)
         B = sums.shape[0]
-        buf = _DeviceBuffer.from_host(sums)
+        buf = _DeviceBuffer.from_host(sums, stream)
         cap = max(B * self.reads.n_reads * capi.TOPHITS_MAX_FIELD, B, 1)
         out = np.empty(cap, np.uint8)
         size = C.c_size_t(cap)
         try:
-            _ck(capi.lib().gmg_tophits_format_rows(self.h, buf.ptr, B, int(bool(forward_only)), _ptr(out), C.byref(size), None))
+            _ck(capi.lib().gmg_tophits_format_rows(self.h, buf.ptr, B, int(bool(forward_only)), _ptr(out), C.byref(size), stream))
         finally:
             buf.free()
         return out[:size.value].tobytes()
@@ -1364,19 +1379,18 @@ class TopHits:
             pass
 
 
-def window_distrib(model, windows, frames):
-    """Full_Window_Distrib / Full_Window_Prob (icm.cc:512-610).  windows: uint8 codes [n, model_len]
+def window_distrib(model, windows, frames, stream=None):
+    """Full_Window_Distrib / Full_Window_Prob (icm.cc:512-610) on `stream`.  windows: uint8 codes [n, model_len]
     -> (dist float32 [n,4], prob float64 [n])"""
     windows = np.ascontiguousarray(windows, np.uint8)
     n = windows.shape[0]
-    dw = _DeviceBuffer.from_host(windows)
-    df = _DeviceBuffer.from_host(np.asarray(frames, np.int32))
+    dw = _DeviceBuffer.from_host(windows, stream)
+    df = _DeviceBuffer.from_host(np.asarray(frames, np.int32), stream)
     dd = _DeviceBuffer(max(n, 1) * 16)
     dp = _DeviceBuffer(max(n, 1) * 8)
-    _ck(capi.lib().gmg_window_distrib(model.device(), dw.ptr, df.ptr, n, dd.ptr, dp.ptr, None))
-    _ck(capi.lib().gmg_synchronize(None))
-    dist = dd.to_host(np.float32, 4 * n).reshape(n, 4)
-    prob = dp.to_host(np.float64, n)
+    _ck(capi.lib().gmg_window_distrib(model.device(), dw.ptr, df.ptr, n, dd.ptr, dp.ptr, stream))
+    dist = dd.to_host(np.float32, 4 * n, stream).reshape(n, 4)
+    prob = dp.to_host(np.float64, n, stream)
     for b in (dw, df, dd, dp):
         b.free()
     return dist, prob
@@ -1492,8 +1506,7 @@ def fixed_score(model, reads, segs, lo=0, hi=None, d_out=None, stream=None):
         _ck(capi.lib().gmg_fixed_score(h, reads.h, segs.h, int(lo), int(hi), C.c_void_p(d_out), stream))
         return None
     buf = _DeviceBuffer(max(segs.n, 1) * 8)
-    _ck(capi.lib().gmg_fixed_score(h, reads.h, segs.h, int(lo), int(hi), buf.ptr, None))
-    _ck(capi.lib().gmg_synchronize(None))
-    out = buf.to_host(np.float64, segs.n)
+    _ck(capi.lib().gmg_fixed_score(h, reads.h, segs.h, int(lo), int(hi), buf.ptr, stream))
+    out = buf.to_host(np.float64, segs.n, stream)
     buf.free()
     return out

@@ -255,6 +255,7 @@ PROTOTYPES = {
 # debug exports: not declared in include/*.h
 DEBUG_PROTOTYPES = {
     "gmg_debug_cache_stats": (i32, [vp]),   # out[4]: busy blocks, busy bytes, idle blocks, idle bytes of the device block cache
+    "gmg_debug_stall": (i32, [vp, C.c_uint32]),   # (stream, microseconds <= 250 000): one wave that holds the stream back (tests/test_gpu_streams.py)
 }
 
 

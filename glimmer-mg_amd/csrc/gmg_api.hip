@@ -364,6 +364,7 @@ extern "C" int gmg_model_upload(const int16_t *mip, const float *prob4, int W, i
     if (!m) return gmg_set_error(GMG_ENOMEM, "gmg_model_upload: out of host memory");
     GMG_HIP(m->own.alloc(&m->d_blob, total));
     GMG_HIP(hipMemcpy(m->d_blob, blob.data(), total, hipMemcpyHostToDevice));
+    GMG_HANDLE_READY();
     m->min_exp = 255;
     m->max_exp = 0;
     m->odd_values = 0;
@@ -424,6 +425,7 @@ extern "C" int gmg_null_set_upload(const gmg_model *const *models, int n, gmg_nu
         GMG_HIP(hipMemcpy(ns->d_tab + (size_t)i * 252, models[i]->dev.dense, 192 * sizeof(float), hipMemcpyDeviceToDevice));
         GMG_HIP(hipMemcpy(ns->d_tab + (size_t)i * 252 + 192, models[i]->dev.dense_part, 60 * sizeof(float), hipMemcpyDeviceToDevice));
     }
+    GMG_HANDLE_READY();                                 // (device-to-device copies need not block the host)
     *out = ns.release();
     return GMG_OK;
 }
@@ -467,6 +469,7 @@ extern "C" int gmg_null_set_from_tables(const int16_t *mip, const float *prob4, 
         }
     GMG_HIP(ns->own.alloc(&ns->d_tab, tab.size() * sizeof(float)));
     GMG_HIP(hipMemcpy(ns->d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    GMG_HANDLE_READY();
     *out = ns.release();
     return GMG_OK;
 }
@@ -942,6 +945,7 @@ extern "C" int gmg_segments_upload(const gmg_reads *reads, const gmg_segment *se
     GMG_HIP(own.alloc(&d_out_off, (n + 1) * 8));
     if (n) GMG_HIP(hipMemcpy(d_segs, segs, n * sizeof(gmg_segment), hipMemcpyHostToDevice));
     GMG_HIP(hipMemcpy(d_out_off, pre.data(), (n + 1) * 8, hipMemcpyHostToDevice));
+    GMG_HANDLE_READY();
     gmg_segments *g = new (std::nothrow) gmg_segments();
     if (!g) return gmg_set_error(GMG_ENOMEM, "gmg_segments_upload: out of host memory");
     g->d_segs = d_segs;
@@ -1224,6 +1228,35 @@ extern "C" int gmg_debug_cache_stats(uint64_t out[4])
         out[b.busy ? 0 : 2]++;
         out[b.busy ? 1 : 3] += b.bytes;
     }
+    return GMG_OK;
+}
+
+// tests (tests/test_gpu_streams.py): hold `stream` back for `microseconds` (at most GMG_STALL_MAX_US), so that what is queued behind
+// the stall demonstrably has not run while the host goes on.  One wave that reads the device's constant-rate wall clock between
+// sleeps and touches no memory; it also ends after GMG_STALL_MAX_ITER rounds, whatever the clock does (a round is a sleep of 32 x 64
+// cycles or more: 2^31 cycles in all, which is beyond the longest stall at any shader clock below 8 GHz and about a second at 2.4 GHz).
+#define GMG_STALL_MAX_US 250000u
+#define GMG_STALL_MAX_ITER (1 << 20)
+__global__ __launch_bounds__(64) void k_debug_stall(unsigned long long ticks)
+{
+    const unsigned long long t0 = wall_clock64();
+    for (int i = 0; i < GMG_STALL_MAX_ITER; i++) {
+        if (wall_clock64() - t0 >= ticks) break;
+        __builtin_amdgcn_s_sleep(32);
+    }
+}
+
+extern "C" int gmg_debug_stall(void *stream, uint32_t microseconds)
+{
+    if (microseconds > GMG_STALL_MAX_US)
+        return gmg_set_error(GMG_EINVAL, "gmg_debug_stall: %u microseconds, at most %u", microseconds, GMG_STALL_MAX_US);
+    { int rc = gmg_enter("gmg_debug_stall"); if (rc) return rc; }
+    int khz = 0;
+    GMG_HIP(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, g_device));
+    if (khz <= 0) return gmg_set_error(GMG_EHIP, "gmg_debug_stall: the device reports no wall clock rate");
+    const unsigned long long ticks = ((unsigned long long)microseconds * (unsigned long long)khz + 999) / 1000;
+    hipLaunchKernelGGL(k_debug_stall, dim3(1), dim3(64), 0, (hipStream_t)stream, ticks);
+    GMG_HIP(hipGetLastError());
     return GMG_OK;
 }
 

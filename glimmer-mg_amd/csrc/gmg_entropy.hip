@@ -155,9 +155,9 @@ extern "C" int gmg_entropy_regions(const gmg_reads *reads, const gmg_gene_region
     if (rc) return rc;
     if (n == 0 || (!d_counts && !d_dist)) return GMG_OK;
     hipStream_t s = (hipStream_t)stream;
-    // read lengths are needed for validation: fetch the offsets once
+    // read lengths are needed for validation: fetch the offsets once, on the call's stream
     std::vector<uint64_t> off(reads->n_reads + 1);
-    GMG_HIP(hipMemcpy(off.data(), reads->d_off, off.size() * 8, hipMemcpyDeviceToHost));
+    GMG_HIP(gmg_copy_wait(off.data(), reads->d_off, off.size() * 8, hipMemcpyDeviceToHost, s));
     for (uint64_t i = 0; i < n; i++) {
         const gmg_gene_region &r = regions[i];
         if (r.read >= reads->n_reads)

@@ -165,7 +165,7 @@ extern "C" int gmg_reads_extract(const gmg_reads *reads, const gmg_gene_region *
     std::vector<ExtPatch> patches;
     if (n_amb && n) {
         std::vector<uint64_t> src_off(reads->n_reads + 1), new_off(n + 1);
-        GMG_HIP(hipMemcpy(src_off.data(), reads->d_off, src_off.size() * 8, hipMemcpyDeviceToHost));
+        GMG_HIP(gmg_copy_wait(src_off.data(), reads->d_off, src_off.size() * 8, hipMemcpyDeviceToHost, s));
         new_off[0] = 0;
         for (uint64_t k = 0; k < n; k++) new_off[k + 1] = new_off[k] + (uint64_t)regions[k].len;
         ext_patches(regions, n, reversed, src_off.data(), new_off.data(), amb_base, amb_rev_code, n_amb, patches);

@@ -439,13 +439,16 @@ extern "C" int gmg_features_count(const gmg_reads *reads, const gmg_feature_gene
             group_read.push_back(r);
         }
     }
-    struct Pinned { uint64_t *p = nullptr; ~Pinned() { if (p) (void)hipHostFree(p); } } ext;     // [2 * groups]: begin, end
+    // [2 * groups]: begin, end.  Pageable: hipHostFree of a page-locked buffer waits for the whole device, the null stream included,
+    // which a call on a caller's stream must not
+    struct Extents { std::vector<uint64_t> v; uint64_t *p = nullptr; } ext;
     {
+        ext.v.resize(2 * group_read.size() + 1);
+        ext.p = ext.v.data();
         uint32_t *d_group_read = nullptr;
         uint64_t *d_ext = nullptr;
         GMG_HIP(sc.alloc(&d_group_read, group_read.size() * 4));
         GMG_HIP(sc.alloc(&d_ext, group_read.size() * 16));
-        GMG_HIP(hipHostMalloc((void **)&ext.p, group_read.size() * 16, hipHostMallocDefault));
         GMG_HIP(hipMemcpyAsync(d_group_read, group_read.data(), group_read.size() * 4, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_feat_group_extent, dim3((unsigned)((group_read.size() + 255) / 256)), dim3(256), 0, s, reads->d_off, d_group_read,
                            (uint32_t)group_read.size(), d_ext);

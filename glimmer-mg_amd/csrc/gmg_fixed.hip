@@ -195,6 +195,7 @@ extern "C" int gmg_fixed_model_upload(int L, const int32_t *perm, const int16_t 
     m->blob_bytes = bytes;
     GMG_HIP(m->own.alloc(&m->d_blob, bytes));
     GMG_HIP(hipMemcpy(m->d_blob, h.data(), bytes, hipMemcpyHostToDevice));
+    GMG_HANDLE_READY();
     m->d_prob = (float4 *)m->d_blob;
     m->d_mip = (int8_t *)((unsigned char *)m->d_blob + total * sizeof(float4));
     *out = m.release();

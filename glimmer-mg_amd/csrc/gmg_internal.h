@@ -185,6 +185,7 @@ struct GMG_HIDDEN gmg_mg_result {
     gmg_start_errors *d_errs = nullptr;  // error branch only: parallel to d_starts
     uint64_t *d_read_orf_off = nullptr;  // [n_reads + 1]
     uint64_t n_reads = 0, n_orfs = 0, n_starts = 0;
+    hipStream_t s = nullptr;     // the stream the call ran on (it has waited for it): gmg_mg_result_fetch_errors copies on it
     GmgScratch own;              // (the caller has waited for the result's stream before it frees the result)
 };
 
@@ -215,6 +216,17 @@ int gmg_enter(const char *who);
             return gmg_set_error(e_ == hipErrorOutOfMemory ? GMG_ENOMEM : GMG_EHIP, "%s failed: %s (%s:%d)", #call, \
                                  hipGetErrorString(e_), __FILE__, __LINE__);                  \
     } while (0)
+
+// The stream contract.  A copy the host waits for inside a stream-taking call goes on THAT stream: a caller's
+// non-blocking stream is not ordered with the null stream, and a synchronous hipMemcpy would wait for whatever the null stream holds.
+static inline hipError_t gmg_copy_wait(void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t s)
+{
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, s);
+    return e != hipSuccess ? e : hipStreamSynchronize(s);
+}
+// A constructor without a stream parameter works on the null stream and returns a handle that any stream may use at once: hipMemset
+// and device-to-device hipMemcpy need not block the host, so the constructor waits for the null stream before it returns.
+#define GMG_HANDLE_READY() GMG_HIP(hipStreamSynchronize(0))
 
 // Tuning / test switches (gmg_set_option, include/gmg.h).  Set explicitly through the API, or once at gmg_init() from the
 // environment variable GMG_<NAME IN UPPER CASE>; never read from the environment on a scoring path.

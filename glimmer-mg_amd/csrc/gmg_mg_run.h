@@ -537,6 +537,7 @@ struct MgRun {
         res = new (std::nothrow) gmg_mg_result();
         if (!res) { sc.wait = GmgScratch::NONE; return gmg_set_error(GMG_ENOMEM, "gmg_mg_score_reads: out of host memory"); }
         res->n_reads = reads->n_reads;
+        res->s = s;
         if (!p.find_only) {                                 // 1. Frame_Scores
             if (prm->nulls && !p.nul_dense3) return gmg_set_error(GMG_EBADMODEL, "gmg_mg_score_reads: per-read null models are (3,2,3) models");
             MG_STAGE(upload_tables());
@@ -1114,7 +1115,7 @@ struct MgRun {
     int count_overflow(int &level_tries, bool &again)
     {
         uint32_t st[32];
-        MG_TRY(hipMemcpy(st, d_err_flag, 128, hipMemcpyDeviceToHost));
+        MG_TRY(gmg_copy_wait(st, d_err_flag, 128, hipMemcpyDeviceToHost, s));
         const bool err_tile = p.err_tile, err_wave = p.err_wave;
         if (tm.on && err_tile) fprintf(stderr, "[gmg_mg] k_mg_err_tile: %u tiles (%llu ORFs)\n", st[18], (unsigned long long)no);
         if (tm.on && err_wave)
@@ -1337,7 +1338,7 @@ struct MgRun {
         tm.lap("start lists");
         if (p.err_wave && res->n_orfs && d_err_flag) {      // did a wave's stack overflow in the WRITE pass?  (the count pass was checked behind its scan)
             uint32_t flag = 0;
-            MG_TRY(hipMemcpy(&flag, d_err_flag, 4, hipMemcpyDeviceToHost));
+            MG_TRY(gmg_copy_wait(&flag, d_err_flag, 4, hipMemcpyDeviceToHost, s));
             if (flag) return MG_RETRY_NO_WAVE;
         }
         return GMG_OK;
@@ -1426,7 +1427,7 @@ extern "C" int gmg_mg_result_fetch_errors(const gmg_mg_result *r, gmg_start_erro
     if (!r || (r->n_starts && !errs)) return gmg_set_error(GMG_EINVAL, "gmg_mg_result_fetch_errors: NULL argument");
     if (!r->n_starts) return GMG_OK;
     if (!r->d_errs) { memset(errs, 0, r->n_starts * sizeof(gmg_start_errors)); return GMG_OK; }
-    GMG_HIP(hipMemcpy(errs, r->d_errs, r->n_starts * sizeof(gmg_start_errors), hipMemcpyDeviceToHost));
+    GMG_HIP(gmg_copy_wait(errs, r->d_errs, r->n_starts * sizeof(gmg_start_errors), hipMemcpyDeviceToHost, r->s));
     return GMG_OK;
 }
 

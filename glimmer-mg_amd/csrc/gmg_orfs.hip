@@ -1054,6 +1054,7 @@ extern "C" int gmg_orfs_upload(const gmg_reads *reads, const gmg_orf *orfs, uint
     GMG_HIP(hipMemset(b->d_nst, 0, (n + 1) * 4));
     if (n) GMG_HIP(hipMemcpy(b->d_orfs, orfs, n * sizeof(gmg_orf), hipMemcpyHostToDevice));
     GMG_HIP(hipMemcpy(b->d_start_off, start_off.data(), (n + 1) * 8, hipMemcpyHostToDevice));
+    GMG_HANDLE_READY();
     if (out_max_starts) *out_max_starts = b->max_starts;
     *out = b.release();
     return GMG_OK;

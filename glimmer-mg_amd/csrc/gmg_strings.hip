@@ -248,10 +248,14 @@ extern "C" int gmg_score_reads_strings(const gmg_model *const *models, int n_mod
     hipStream_t s = (hipStream_t)stream;
     const uint64_t nr = reads->n_reads;
     if (nr == 0 || n_models == 0) return GMG_OK;
-    GmgScratch sc(GmgScratch::STREAM, s);               // the scratch goes back to the cache once nothing queued may still use it
+    std::vector<gmg_segment> sg;                        // (sources of copies on s: they outlive sc, whose end waits for s)
+    std::vector<uint64_t> pre;
+    GmgScratch sc(GmgScratch::STREAM, s);              // the scratch goes back to the cache once nothing queued may still use it
     float *d_vals = nullptr, *d_heads = nullptr;
     uint32_t *d_redo = nullptr;                         // [1 + 2 nr]: counter, list
-    struct Segs { gmg_segments *p = nullptr; ~Segs() { gmg_segments_free(p); } } segs;   // built on demand for models without the fast pass
+    // (read, FORWARD) and (read, REVCOMP) segments, built on demand for models without the fast pass: a view over two blocks of the
+    // call's scratch, filled on the call's stream (gmg_segments_upload is a constructor: null stream, and its free waits for the device)
+    gmg_segments segs = {nullptr, nullptr, 0, 0, 0};
     for (int k = 0; k < n_models; k++) {
         const gmg_model *m = models[k];
         if (!m) return gmg_set_error(GMG_EINVAL, "gmg_score_reads_strings: model %d is NULL", k);
@@ -321,19 +325,29 @@ extern "C" int gmg_score_reads_strings(const gmg_model *const *models, int n_mod
         }
         if (fast != GMG_EBADMODEL) return fast;
         // any other model shape: the exact segment kernel on (read, FORWARD) and (read, REVCOMP) segments
-        if (!segs.p) {
+        if (!segs.d_segs) {
             std::vector<uint64_t> off(nr + 1);
-            GMG_HIP(hipMemcpy(off.data(), reads->d_off, (nr + 1) * 8, hipMemcpyDeviceToHost));
-            std::vector<gmg_segment> sg(2 * nr);
+            GMG_HIP(gmg_copy_wait(off.data(), reads->d_off, (nr + 1) * 8, hipMemcpyDeviceToHost, s));
+            sg.resize(2 * nr);
+            pre.assign(2 * nr + 1, 0);
+            uint64_t min_len = UINT64_MAX;
             for (uint64_t r = 0; r < nr; r++) {
                 const uint32_t len = (uint32_t)(off[r + 1] - off[r]);
                 sg[2 * r] = {(uint32_t)r, 0, len, GMG_FORWARD};
                 sg[2 * r + 1] = {(uint32_t)r, 0, len, GMG_REVCOMP};
+                pre[2 * r + 1] = pre[2 * r] + len;
+                pre[2 * r + 2] = pre[2 * r + 1] + len;
+                if (len < min_len) min_len = len;
             }
-            const int rc = gmg_segments_upload(reads, sg.data(), 2 * nr, nullptr, nullptr, &segs.p);
-            if (rc) return rc;
+            GMG_HIP(sc.alloc(&segs.d_segs, 2 * nr * sizeof(gmg_segment)));
+            GMG_HIP(sc.alloc(&segs.d_out_off, (2 * nr + 1) * 8));
+            GMG_HIP(hipMemcpyAsync(segs.d_segs, sg.data(), 2 * nr * sizeof(gmg_segment), hipMemcpyHostToDevice, s));
+            GMG_HIP(hipMemcpyAsync(segs.d_out_off, pre.data(), (2 * nr + 1) * 8, hipMemcpyHostToDevice, s));
+            segs.n = 2 * nr;
+            segs.total_len = pre[2 * nr];
+            segs.min_len = min_len;
         }
-        const int rc = gmg_score_string(m, reads, segs.p, 0, out, s);
+        const int rc = gmg_score_string(m, reads, &segs, 0, out, s);
         if (rc) return rc;
     }
     GMG_HIP(hipStreamSynchronize(s));

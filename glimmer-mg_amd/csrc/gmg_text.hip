@@ -207,6 +207,7 @@ extern "C" int gmg_letters_upload(const char *letters, const uint64_t *base_offs
     if (!l) return gmg_set_error(GMG_ENOMEM, "gmg_letters_upload: out of host memory");
     GMG_HIP(l->own.alloc(&l->d_letters, total ? total : 1));
     if (total) GMG_HIP(hipMemcpy(l->d_letters, letters, total, hipMemcpyHostToDevice));
+    GMG_HANDLE_READY();
     GMG_HIP(hipEventCreate(&l->ev[0]));
     GMG_HIP(hipEventCreate(&l->ev[1]));
     l->off.assign(base_offsets, base_offsets + n_reads + 1);

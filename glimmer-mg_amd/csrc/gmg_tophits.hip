@@ -40,6 +40,7 @@ struct GMG_HIDDEN gmg_tophits {
     uint64_t *d_off = nullptr;   // [cap_off] their exclusive sums
     char *d_text = nullptr;      // [cap_text]
     size_t cap_inf = 0, cap_sums = 0, cap_items = 0, cap_off = 0, cap_text = 0;
+    hipStream_t last = nullptr;  // the stream of the last update (the null stream before the first): gmg_tophits_fetch copies on it
     GmgScratch own{GmgScratch::NONE, nullptr, GmgScratch::DRIVER};
 };
 
@@ -223,6 +224,7 @@ extern "C" int gmg_tophits_create(const gmg_reads *reads, int top_hits, gmg_toph
     GMG_HIP(hipMemset(h->d_keys, 0, slots * 8));
     GMG_HIP(hipMemset(h->d_models, 0xff, slots * 4));
     GMG_HIP(hipMemset(h->d_flag, 0, 4));
+    GMG_HANDLE_READY();                                 // (an update on a caller's non-blocking stream is not ordered behind the three memsets)
     *out = h.release();
     return GMG_OK;
 }
@@ -243,6 +245,7 @@ extern "C" int gmg_tophits_update_sums(gmg_tophits *h, const double *d_sums, int
         return gmg_set_error(GMG_EINVAL, "gmg_tophits_update_sums: model indices %d + %d outside int32", first_model, B);
     hipStream_t s = (hipStream_t)stream;
     if (B == 0 || h->n_reads == 0) return GMG_OK;
+    h->last = s;
     const uint8_t *d_inf = nullptr;
     if (informative) {
         GMG_HIP(h->own.regrow(h->d_inf, h->cap_inf, (size_t)B));
@@ -278,8 +281,9 @@ extern "C" int gmg_tophits_fetch(const gmg_tophits *h, int64_t *keys, int32_t *m
     if (nr == 0) return GMG_OK;
     std::vector<int64_t> k(T * nr);
     std::vector<int32_t> m(T * nr);
-    GMG_HIP(hipMemcpy(k.data(), h->d_keys, T * nr * 8, hipMemcpyDeviceToHost));
-    GMG_HIP(hipMemcpy(m.data(), h->d_models, T * nr * 4, hipMemcpyDeviceToHost));
+    // on the stream that wrote the slots last (every update waits for its stream, so they are complete): not behind the null stream's work
+    GMG_HIP(hipMemcpyAsync(k.data(), h->d_keys, T * nr * 8, hipMemcpyDeviceToHost, h->last));
+    GMG_HIP(gmg_copy_wait(m.data(), h->d_models, T * nr * 4, hipMemcpyDeviceToHost, h->last));
     for (uint64_t r = 0; r < nr; r++)                   // slot-major on the device, read-major for the caller
         for (uint64_t i = 0; i < T; i++) {
             keys[r * T + i] = k[i * nr + r];

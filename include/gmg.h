@@ -15,8 +15,17 @@
  *   - "d_" pointers are device (HBM) pointers owned by the caller (hipMalloc /
  *     torch); all other pointers are host memory, caller-owned.
  *   - handles (gmg_model, gmg_reads, gmg_segments) own their device memory.
- *   - `stream` is a hipStream_t passed as void* (NULL = the default stream);
- *     launches are stream-ordered and asynchronous.
+ *   - `stream` is a hipStream_t passed as void* (NULL = the default stream; gmg_stream_create
+ *     hands out non-blocking ones, which are NOT ordered with the default stream).  Every
+ *     kernel, copy and memset of a call that takes a stream runs on that stream or on side
+ *     streams joined to it by events; nothing goes through the default stream.  Whether a
+ *     call returns before its work is done is said per entry point (DESIGN.md 2.3 has the
+ *     table): the scoring calls that write to d_ pointers do, the calls that return host
+ *     results or result handles wait for the stream.
+ *   - an entry point WITHOUT a stream parameter that makes a handle (the _upload, _create,
+ *     _wrap_device, _select, _extract, _splice, _build, _from_tables calls) works on the
+ *     default stream and has waited for it when it returns: the handle may be used on any
+ *     stream at once.
  *   - base code: a=0 c=1 g=2 t=3 (ALPHA_STRING, src/ICM/icm.hh:30), complement
  *     = 3 - code.  Packed reads hold 16 bases per uint32, base g of the job at
  *     bits [2*(g%16), 2*(g%16)+1] of word g/16, reads concatenated without
@@ -673,7 +682,8 @@ int gmg_mg_result_info(const gmg_mg_result *r, uint64_t *n_orfs, uint64_t *n_sta
 /* Copies the result to HOST buffers: orfs[n_orfs], starts[n_starts] and, if not NULL,
  * read_orf_off[n_reads + 1] (ORFs of read i are orfs[read_orf_off[i] .. read_orf_off[i+1])). */
 int gmg_mg_result_fetch(const gmg_mg_result *r, gmg_mg_orf *orfs, gmg_start *starts, uint64_t *read_orf_off);
-/* Error branch: errs[n_starts], parallel to starts (all-zero entries without the error flags). */
+/* Error branch: errs[n_starts], parallel to starts (all-zero entries without the error flags); copied on the stream the scoring
+ * call ran on, which must still exist. */
 int gmg_mg_result_fetch_errors(const gmg_mg_result *r, gmg_start_errors *errs);
 /* the same copies on `stream` (they then overlap the scoring of the next batch on another stream) */
 int gmg_mg_result_fetch_on(const gmg_mg_result *r, gmg_mg_orf *orfs, gmg_start *starts, uint64_t *read_orf_off,
@@ -778,7 +788,8 @@ int gmg_xlate_table(int code, char aa[64]);
 typedef struct gmg_gene_region { uint32_t read; int32_t first, len, strand; } gmg_gene_region;
 /* regions: HOST array.  d_counts [n][20] int32 and d_dist [n][3] double {pos_dist, neg_dist, ratio}: DEVICE, either may be NULL.
  * first in [0, read length), 0 <= len <= read length, strand != 0: GMG_ERANGE otherwise; an aa entry that is neither 'A'..'Z' nor
- * '*': GMG_EINVAL.  Stream-ordered and asynchronous. */
+ * '*': GMG_EINVAL.  Stream-ordered: the call waits once for `stream` (the read lengths come back over it for the checks), then
+ * queues its kernel and returns; its scratch goes back to the library's cache behind that kernel. */
 int gmg_entropy_regions(const gmg_reads *reads, const gmg_gene_region *regions, uint64_t n, const char aa[64],
                         const double pos[20], const double neg[20], int32_t *d_counts, double *d_dist, void *stream);
 /* the same for every ORF of a gmg_find_orfs / gmg_mg_score_reads result, which stays on the device: ORF k's region by
@@ -931,7 +942,8 @@ int gmg_tophits_update_sums(gmg_tophits *h, const double *d_sums, int B, int fir
  * *d_sums_out (may be NULL) = that buffer, valid until the next call on the handle */
 int gmg_tophits_scores(gmg_tophits *h, const gmg_model *const *models, int B, int first_model, const uint8_t *informative,
                        int forward_only, void *stream, const double **d_sums_out);
-/* the slots (HOST, [n_reads][top_hits]): keys (the %.4f value x 10^4) and model indices; an empty slot has model -1 */
+/* the slots (HOST, [n_reads][top_hits]): keys (the %.4f value x 10^4) and model indices; an empty slot has model -1.  Copied on the
+ * stream of the handle's last update (the default stream before the first), which must still exist, and waited for. */
 int gmg_tophits_fetch(const gmg_tophits *h, int64_t *keys, int32_t *models);
 /* The B data-matrix lines of the raw file for d_sums (device, [B][n_reads][2]): per model one line, per read the winning
  * strand's %.4f text, tab-separated, ending in a newline -- formatted on the device.  *bytes: in = capacity of host_out, out =

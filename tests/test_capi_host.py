@@ -42,6 +42,21 @@ def test_debug_owned_blocks_is_declared_and_bound(gmg):
     assert gmg.capi.lib().gmg_debug_owned_blocks(None) == -1
 
 
+def test_debug_stall_is_bound_outside_the_headers_and_refuses_long_stalls(gmg):
+    """the stream tests' bounded stall (tests/test_gpu_streams.py): not declared in include/*.h, bound in capi.py beside
+    gmg_debug_cache_stats, and a stall above 250 000 microseconds is GMG_EINVAL before anything touches a device"""
+    for hdr in ("gmg.h", "gmg_icm.h"):
+        assert "gmg_debug_stall" not in open(os.path.join(ROOT, "include", hdr)).read()
+    assert "gmg_debug_stall" not in gmg.capi.PROTOTYPES
+    assert gmg.capi.DEBUG_PROTOTYPES["gmg_debug_stall"] == (C.c_int, [C.c_void_p, C.c_uint32])
+    lib = gmg.capi.lib()
+    for us in (250_001, 1_000_000, 2**32 - 1):
+        assert lib.gmg_debug_stall(None, us) == -1, us
+        assert b"at most 250000" in lib.gmg_last_error()
+    if lib.gmg_device_count() == 0:                                  # in range: only the missing device refuses it
+        assert lib.gmg_debug_stall(None, 250_000) == -2
+
+
 def test_base_code_matches_filter_subscript(gmg, oracle):
     lib = gmg.capi.lib()
     for ch in range(1, 128):
