@@ -256,6 +256,8 @@ PROTOTYPES = {
 DEBUG_PROTOTYPES = {
     "gmg_debug_cache_stats": (i32, [vp]),   # out[4]: busy blocks, busy bytes, idle blocks, idle bytes of the device block cache
     "gmg_debug_stall": (i32, [vp, C.c_uint32]),   # (stream, microseconds <= 250 000): one wave that holds the stream back (tests/test_gpu_streams.py)
+    "gmg_debug_thread_streams": (i32, [C.POINTER(u64)]),   # live streams + events the library made for host threads (tests/test_gpu_threads.py)
+    "gmg_debug_icm_score_string": (i32, [vp, C.c_char_p, i32, i32, C.POINTER(C.c_double)]),   # (gmg_icm, string, len, frame, out): ICM_t::Score_String on the calling thread's staging
 }
 
 

@@ -1206,6 +1206,16 @@ extern "C" int gmg_debug_owned_blocks(uint64_t *out)
     return GMG_OK;
 }
 
+// tests (tests/test_gpu_threads.py): the live streams and events the library has made for host threads -- the side streams of
+// gmg_mg_score_reads (MgStreamSet, gmg_mg_run.h), one set per (thread, device).  A thread that has ended holds none.
+std::atomic<long long> g_gmg_thread_streams{0};
+extern "C" int gmg_debug_thread_streams(uint64_t *out)
+{
+    if (!out) return gmg_set_error(GMG_EINVAL, "gmg_debug_thread_streams: NULL argument");
+    *out = (uint64_t)g_gmg_thread_streams.load();
+    return GMG_OK;
+}
+
 extern "C" int gmg_trim_cache(void)
 {
     std::lock_guard<std::mutex> lock(g_pool_mutex);

@@ -65,6 +65,7 @@ void gmg_pool_release_after(void *p, hipStream_t s);   // ... once the work queu
 // library's exports)
 #define GMG_HIDDEN __attribute__((visibility("hidden")))
 GMG_HIDDEN extern std::atomic<long long> g_gmg_owned_blocks;   // live DRIVER blocks (gmg_debug_owned_blocks)
+GMG_HIDDEN extern std::atomic<long long> g_gmg_thread_streams; // live streams + events made for host threads (gmg_debug_thread_streams)
 struct GMG_HIDDEN GmgScratch {
     enum Wait { NONE, STREAM, DEVICE, AFTER };
     enum Source { CACHE, DRIVER };

@@ -441,12 +441,23 @@ static MgPlan mg_plan(const gmg_model *gene, const gmg_model *nul, const MgGroup
 }
 
 // The side streams of one (host thread, device), made when a call first needs them and kept: a set counts as made only when all
-// of it exists.
+// of it exists.  The set is the thread's (thread_local, below): when the thread ends its destructor gives streams and events back,
+// as Thread_Staging_t (host/icm.cc) does with the thread's staging.  No call of the thread is running then, and every call has
+// joined the side streams into the caller's stream and waited for that one (MgRun::finish), so nothing is queued on them.
 template <int NS, int NE>
 struct MgStreamSet {
     hipStream_t st[NS] = {};
     hipEvent_t ev[NE] = {};
     bool made = false;
+    MgStreamSet() {}
+    MgStreamSet(const MgStreamSet &) = delete;
+    MgStreamSet &operator=(const MgStreamSet &) = delete;
+    ~MgStreamSet()
+    {
+        if (!made) return;
+        drop();                                         // (the main thread's set goes at process exit: whatever HIP answers then is ignored)
+        g_gmg_thread_streams -= NS + NE;
+    }
     hipError_t need(const bool low_priority, const int prio)
     {
         if (made) return hipSuccess;
@@ -455,11 +466,16 @@ struct MgStreamSet {
             e = low_priority ? hipStreamCreateWithPriority(&st[k], hipStreamNonBlocking, prio) : hipStreamCreateWithFlags(&st[k], hipStreamNonBlocking);
         for (int k = 0; k < NE && e == hipSuccess; k++) e = hipEventCreateWithFlags(&ev[k], hipEventDisableTiming);
         made = e == hipSuccess;
-        if (!made) {
-            for (int k = 0; k < NS; k++) { if (st[k]) (void)hipStreamDestroy(st[k]); st[k] = nullptr; }
-            for (int k = 0; k < NE; k++) { if (ev[k]) (void)hipEventDestroy(ev[k]); ev[k] = nullptr; }
-        }
+        if (made) g_gmg_thread_streams += NS + NE;
+        else drop();
         return e;
+    }
+private:
+    void drop()
+    {
+        for (int k = 0; k < NS; k++) { if (st[k]) (void)hipStreamDestroy(st[k]); st[k] = nullptr; }
+        for (int k = 0; k < NE; k++) { if (ev[k]) (void)hipEventDestroy(ev[k]); ev[k] = nullptr; }
+        made = false;
     }
 };
 struct MgStreams {

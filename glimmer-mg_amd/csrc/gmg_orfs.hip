@@ -1067,13 +1067,16 @@ extern "C" int gmg_orf_batch_free(gmg_orf_batch *b)
     return GMG_OK;
 }
 
+static int orfs_begin(const gmg_model *gene, const gmg_model *nul, const gmg_reads *reads, const gmg_orf_batch *b,
+                      const gmg_orf_params *prm, uint64_t *out_n_starts, void *stream, const bool wait_packed);
+
 extern "C" int gmg_score_orfs(const gmg_model *gene, const gmg_model *nul, const gmg_reads *reads,
                               const gmg_orf_batch *b, const gmg_orf_params *prm, gmg_orf_result *results,
                               gmg_start *starts, void *stream)
 {
     if ((b && b->n && !results) || (b && b->max_starts && !starts)) return gmg_set_error(GMG_EINVAL, "gmg_score_orfs: NULL argument");
     uint64_t n_starts = 0;
-    const int rc = gmg_score_orfs_begin(gene, nul, reads, b, prm, &n_starts, stream);
+    const int rc = orfs_begin(gene, nul, reads, b, prm, &n_starts, stream, false);     // (the fetch follows on the same stream)
     return rc ? rc : gmg_score_orfs_fetch(b, results, starts, stream);
 }
 
@@ -1090,8 +1093,10 @@ extern "C" int gmg_score_orfs_fetch(const gmg_orf_batch *b, gmg_orf_result *resu
     return GMG_OK;
 }
 
-extern "C" int gmg_score_orfs_begin(const gmg_model *gene, const gmg_model *nul, const gmg_reads *reads,
-                                    const gmg_orf_batch *b, const gmg_orf_params *prm, uint64_t *out_n_starts, void *stream)
+// wait_packed: return only when the packed lists are complete, so that a fetch on ANY stream finds them (gmg_score_orfs_begin); the
+// one-call form fetches on the same stream and leaves the order to it
+static int orfs_begin(const gmg_model *gene, const gmg_model *nul, const gmg_reads *reads, const gmg_orf_batch *b,
+                      const gmg_orf_params *prm, uint64_t *out_n_starts, void *stream, const bool wait_packed)
 {
     if (!gene || !nul || !reads || !b || !prm || !out_n_starts)
         return gmg_set_error(GMG_EINVAL, "gmg_score_orfs: NULL argument");
@@ -1257,8 +1262,15 @@ extern "C" int gmg_score_orfs_begin(const gmg_model *gene, const gmg_model *nul,
     hipLaunchKernelGGL(k_orf_compact, dim3(grid), dim3(256), 0, s, b->d_starts, b->d_start_off, b->d_coff, b->d_results,
                        b->d_compact, b->n);
     GMG_HIP(hipGetLastError());
+    if (wait_packed) GMG_HIP(hipStreamSynchronize(s));
     mb->n_packed = total;
     mb->scored = 1;
     *out_n_starts = total;
     return GMG_OK;
+}
+
+extern "C" int gmg_score_orfs_begin(const gmg_model *gene, const gmg_model *nul, const gmg_reads *reads,
+                                    const gmg_orf_batch *b, const gmg_orf_params *prm, uint64_t *out_n_starts, void *stream)
+{
+    return orfs_begin(gene, nul, reads, b, prm, out_n_starts, stream, true);
 }

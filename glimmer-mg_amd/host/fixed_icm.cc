@@ -113,11 +113,15 @@ Fixed_Length_ICM_t :: ~ Fixed_Length_ICM_t  ()
 
 void  Fixed_Length_ICM_t :: Clear  (void)
   {
-   if  (dev_fixed != NULL)
-       {
-        gmg_fixed_model_free (dev_fixed);
-        dev_fixed = NULL;
-       }
+   if  (gmg_host :: Mirror_Load (dev_fixed) != NULL)        //  (a model without a mirror never touches the lock)
+     {
+      std :: lock_guard <std :: mutex>  lock (gmg_host :: Mirror_Mutex ());      //  (not around the sub-models: they take it themselves)
+      if  (dev_fixed != NULL)
+          {
+           gmg_fixed_model_free (dev_fixed);
+           gmg_host :: Mirror_Store (dev_fixed, (gmg_fixed_model *) NULL);
+          }
+     }
    for  (size_t i = 0;  i < sub_model . size ();  i ++)
      delete  sub_model [i];
    sub_model . clear ();
@@ -199,14 +203,22 @@ void  Fixed_Length_ICM_t :: read  (const char * path)
 
 const gmg_fixed_model *  Fixed_Length_ICM_t :: Device_Model  (void)  const
   {
-   if  (dev_fixed == NULL)
+   //  the first use may come from several threads at once: one of them uploads (icm_internal.hh)
+   gmg_fixed_model  * m = gmg_host :: Mirror_Load (dev_fixed);
+   if  (m != NULL)
+       return  m;
+   //  nothing reaches exit () with the lock held (ICM_t::Device_Model says why)
+   if  (sub_model . empty ())
        {
-        if  (sub_model . empty ())
-            {
-             fprintf (stderr, "ERROR:  Fixed_Length_ICM_t used before read\n");
-             exit (EXIT_FAILURE);
-            }
-        Ensure_Device ();
+        fprintf (stderr, "ERROR:  Fixed_Length_ICM_t used before read\n");
+        exit (EXIT_FAILURE);
+       }
+   Ensure_Device ();
+   bool  failed = false;
+   std :: unique_lock <std :: mutex>  lock (gmg_host :: Mirror_Mutex ());
+   m = dev_fixed;
+   if  (m == NULL)
+       {
         vector < vector <short> >  mip (length);
         vector < vector <float> >  prob (length);
         vector <const int16_t *>  mp (length);
@@ -220,11 +232,15 @@ const gmg_fixed_model *  Fixed_Length_ICM_t :: Device_Model  (void)  const
            depth [i] = sub_model [i] -> Get_Model_Depth ();
            nodes [i] = sub_model [i] -> Get_Num_Nodes ();
           }
-        if  (gmg_fixed_model_upload (length, permutation, mp . data (), pp . data (), depth . data (), nodes . data (),
-                                     & dev_fixed) != GMG_OK)
-            Device_Fatal ("gmg_fixed_model_upload");
+        failed = gmg_fixed_model_upload (length, permutation, mp . data (), pp . data (), depth . data (), nodes . data (),
+                                         & m) != GMG_OK;
+        if  (! failed)
+            gmg_host :: Mirror_Store (dev_fixed, m);
        }
-   return  dev_fixed;
+   lock . unlock ();
+   if  (failed)
+       Device_Fatal ("gmg_fixed_model_upload");
+   return  m;
   }
 
 //  The reference's checks on one window (src/ICM/icm.cc:1575-1600, 1617-1642): strncpy (buff, w, length), Permute_String,

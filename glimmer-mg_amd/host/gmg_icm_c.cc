@@ -168,6 +168,22 @@ extern "C" int  gmg_icm_device_model  (const gmg_icm * icm, const gmg_model * * 
   }
 
 
+//  tests (tests/test_gpu_threads.py; not declared in include/*.h): ICM_t::Score_String of one string -- the host class's
+//  one-call-one-launch path, which makes the calling thread's staging (Thread_Staging, icm.cc) at the thread's first call.
+//  A string of length 0 scores 0.0 as in the reference (src/ICM/icm.cc:864-903): no launch, and no staging is made.
+extern "C" int  gmg_debug_icm_score_string  (const gmg_icm * icm, const char * s, int len, int frame, double * out)
+  {
+   int  periodicity = 0;
+   if  (icm == NULL || s == NULL || out == NULL || len < 0 || frame < 0
+          || gmg_icm_params (icm, NULL, NULL, & periodicity, NULL) != GMG_OK || frame >= periodicity)
+       return  gmg_set_error (GMG_EINVAL, "gmg_debug_icm_score_string: bad argument");
+   if  (gmg_device_count () <= 0)
+       return  gmg_set_error (GMG_ENODEV, "gmg_debug_icm_score_string: no HIP device; there is no CPU fallback");
+   * out = icm -> model . Score_String (s, len, frame);
+   return  GMG_OK;
+  }
+
+
 // ---------------------------------------------------------------------------
 // fixed-length ICMs
 // ---------------------------------------------------------------------------

@@ -39,13 +39,19 @@ void  Device_Fatal  (const char * who)
 
 void  Ensure_Device  (void)
   {
-   static bool  ready = false;
-   if  (ready)
-       return;
-   const char  * env = getenv ("GMG_DEVICE");
-   if  (gmg_init (env ? atoi (env) : 0) != GMG_OK)
-       Device_Fatal ("gmg_init");
-   ready = true;
+   static std :: once_flag  once;
+   std :: call_once (once, [] ()
+     {
+      const char  * env = getenv ("GMG_DEVICE");
+      if  (gmg_init (env ? atoi (env) : 0) != GMG_OK)
+          Device_Fatal ("gmg_init");
+     });
+  }
+
+std :: mutex  & Mirror_Mutex  (void)
+  {
+   static std :: mutex  * mu = new std :: mutex ();     //  (never destroyed: models may be freed while the process exits)
+   return  * mu;
   }
 
 //  The calling thread's staging (page-locked host buffer + device buffers of gmg_single), made at the thread's first call and
@@ -194,25 +200,42 @@ void  ICM_t :: Export_Tables  (vector <short> & mip, vector <float> & prob4)  co
 
 const gmg_model *  ICM_t :: Device_Model  (void)  const
   {
-   if  (dev_mirror == NULL)
-       {
-        vector <short>  mip;
-        vector <float>  prob4;
-        Ensure_Device ();
-        Export_Tables (mip, prob4);
-        if  (gmg_model_upload (mip . data (), prob4 . data (), model_len, model_depth,
-                               periodicity, num_nodes, & dev_mirror) != GMG_OK)
-            Device_Fatal ("gmg_model_upload");
-       }
-   return  dev_mirror;
+   //  the first use may come from several threads at once (const scoring methods of a shared model): one of them uploads
+   //  Nothing reaches exit () with the lock held: exit () runs the destructors of models in static storage (the reference's CLIs
+   //  keep theirs there) on this thread, and those take the lock when they have a mirror to drop.
+   gmg_model  * m = gmg_host :: Mirror_Load (dev_mirror);
+   if  (m != NULL)
+       return  m;
+   Ensure_Device ();
+   bool  failed = false;
+     {
+      std :: lock_guard <std :: mutex>  lock (gmg_host :: Mirror_Mutex ());
+      m = dev_mirror;
+      if  (m == NULL)
+          {
+           vector <short>  mip;
+           vector <float>  prob4;
+           Export_Tables (mip, prob4);
+           failed = gmg_model_upload (mip . data (), prob4 . data (), model_len, model_depth,
+                                      periodicity, num_nodes, & m) != GMG_OK;
+           if  (! failed)
+               gmg_host :: Mirror_Store (dev_mirror, m);
+          }
+     }
+   if  (failed)
+       Device_Fatal ("gmg_model_upload");          //  (this thread's own error text)
+   return  m;
   }
 
 void  ICM_t :: Invalidate_Device_Mirror  (void)  const
   {
+   if  (gmg_host :: Mirror_Load (dev_mirror) == NULL)      //  (a model without a mirror never touches the lock)
+       return;
+   std :: lock_guard <std :: mutex>  lock (gmg_host :: Mirror_Mutex ());
    if  (dev_mirror != NULL)
        {
         gmg_model_free (dev_mirror);
-        dev_mirror = NULL;
+        gmg_host :: Mirror_Store (dev_mirror, (gmg_model *) NULL);
        }
   }
 

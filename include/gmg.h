@@ -26,6 +26,17 @@
  *     _wrap_device, _select, _extract, _splice, _build, _from_tables calls) works on the
  *     default stream and has waited for it when it returns: the handle may be used on any
  *     stream at once.
+ *   - host threads: any number of host threads may call any entry point at the same
+ *     time, provided no two calls share a stream (the default stream included) or a mutable handle.
+ *     Mutable handles belong to ONE call at a time: gmg_letters (its device text is valid until the
+ *     next text call), gmg_tophits, gmg_trainer, gmg_single (one per host thread), gmg_orf_batch
+ *     (between _begin and _fetch), gmg_model_set (until _finish).  Const handles may be shared freely:
+ *     gmg_model, gmg_null_set, gmg_fixed_model, gmg_reads, gmg_segments, gmg_mg_result, gmg_fasta,
+ *     gmg_audit, gmg_windows, gmg_gaps, gmg_features, gmg_classes -- and the host classes ICM_t and
+ *     Fixed_Length_ICM_t through their const scoring methods, the first-use upload of their device
+ *     mirror included.  gmg_set_option is process-wide: set options while no call is running.
+ *     gmg_last_error() is the calling thread's own text.  A thread that ends gives back everything
+ *     the library made for it (side streams, events, staging).
  *   - base code: a=0 c=1 g=2 t=3 (ALPHA_STRING, src/ICM/icm.hh:30), complement
  *     = 3 - code.  Packed reads hold 16 bases per uint32, base g of the job at
  *     bits [2*(g%16), 2*(g%16)+1] of word g/16, reads concatenated without
@@ -563,7 +574,8 @@ int gmg_score_orfs(const gmg_model *gene, const gmg_model *null_model, const gmg
 
 /* The same in two steps, for callers that do not want to reserve out_max_starts entries on the host (a slot per in-frame codon
  * of every ORF: ~100 per ORF, of which ~3 % are used): gmg_score_orfs_begin scores and leaves the results on the device,
- * *out_n_starts = the number of starts of all ORFs; gmg_score_orfs_fetch copies results[n_orfs] and starts[*out_n_starts]. */
+ * *out_n_starts = the number of starts of all ORFs; gmg_score_orfs_fetch copies results[n_orfs] and starts[*out_n_starts].
+ * The results are complete when gmg_score_orfs_begin returns: the fetch may use any stream. */
 int gmg_score_orfs_begin(const gmg_model *gene, const gmg_model *null_model, const gmg_reads *reads,
                          const gmg_orf_batch *orfs, const gmg_orf_params *params, uint64_t *out_n_starts, void *stream);
 int gmg_score_orfs_fetch(const gmg_orf_batch *orfs, gmg_orf_result *results, gmg_start *starts, void *stream);

@@ -57,6 +57,28 @@ def test_debug_stall_is_bound_outside_the_headers_and_refuses_long_stalls(gmg):
         assert lib.gmg_debug_stall(None, 250_000) == -2
 
 
+def test_thread_debug_exports_are_bound_outside_the_headers(gmg):
+    """the thread tests' counter of live per-thread streams and events, and their way to the host class's one-string scoring
+    (tests/test_gpu_threads.py): not declared in include/*.h, bound in capi.py beside gmg_debug_stall; the counter answers without a
+    device and no thread of this process has made a side stream without one; the scorer refuses when there is no device"""
+    for name in ("gmg_debug_thread_streams", "gmg_debug_icm_score_string"):
+        for hdr in ("gmg.h", "gmg_icm.h"):
+            assert name not in open(os.path.join(ROOT, "include", hdr)).read()
+        assert name not in gmg.capi.PROTOTYPES and name in gmg.capi.DEBUG_PROTOTYPES
+    assert gmg.capi.DEBUG_PROTOTYPES["gmg_debug_thread_streams"] == (C.c_int, [C.POINTER(C.c_uint64)])
+    lib = gmg.capi.lib()
+    out = C.c_uint64(1 << 63)
+    assert lib.gmg_debug_thread_streams(C.byref(out)) == 0 and out.value < 1 << 16
+    assert lib.gmg_debug_thread_streams(None) == -1 and b"gmg_debug_thread_streams" in lib.gmg_last_error()
+    icm = gmg.Icm.open(os.path.join(DATA, "cluster-4.icm"))
+    score = C.c_double()
+    assert lib.gmg_debug_icm_score_string(icm.h, None, 4, 0, C.byref(score)) == -1
+    assert lib.gmg_debug_icm_score_string(icm.h, b"acgt", 4, 99, C.byref(score)) == -1
+    if lib.gmg_device_count() == 0:
+        assert out.value == 0
+        assert lib.gmg_debug_icm_score_string(icm.h, b"acgt", 4, 0, C.byref(score)) == -2
+
+
 def test_base_code_matches_filter_subscript(gmg, oracle):
     lib = gmg.capi.lib()
     for ch in range(1, 128):
